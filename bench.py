@@ -14,8 +14,17 @@ collective -- and the job time is the MAX over ranks.
 
 Rank 0 prints ONE JSON line.  Besides the contract fields it carries
   roofline      HBM roofline of the fused kernel on this workload (algorithmic bytes / launch time)
+A plain run stops there: set-up, warm-up, the K timed steps, the line.  With --full the
+default workload also measures, as separate runs after the headline,
   cpu_baseline  the oracle's C restatement timed on this box's host cores (N = 1 only)
   sweep         the same kernel at larger batches, where the HBM roofline is the binding limit
+  ...           the MPC-CBF, closed-loop, manipulator, VTOL2D, Backup-CBF and configs[3] / [4] legs (N = 1),
+                the all-gather leg of configs[3] (N > 1)
+
+--dump-outputs DIR writes what the last timed step returned (u, status, h of every agent of
+rank 0's batch) as DIR/<name>.npy; the inputs are seeded, so two builds compare output for output.
+Where status != 0 the solver returns u = NaN (no solution); the dump writes u = 0 there, so every
+array is finite and status says which rows hold no solution.
 """
 import argparse
 import json
@@ -57,11 +66,45 @@ def parse():
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--max-iter", type=int, default=0,
                     help="hetero_fleet: iteration limit of the interior point (0: the classes' default, IPOPT's 3000; 100: rounds 1 - 3)")
-    ap.add_argument("--no-mpc", action="store_true", help="skip the short MPC-CBF leg of the default run")
+    ap.add_argument("--no-mpc", action="store_true", help="--full: skip the MPC-CBF, closed-loop and configs[3] / [4] legs")
     ap.add_argument("--no-limit100", action="store_true",
                     help="interior-point legs: skip the extra timing of the round-3 configuration (one launch, 100 iterations); the counter "
                          "passes of tools/collect_profiles.sh use it so that every dispatch of a leg belongs to a budget solve")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="cbf_qp: after the headline, also run the CPU baseline, the sweep, the pipelined leg, the MPC / closed-loop / "
+                         "configs[3] / configs[4] legs (one GPU) or the all-gather leg (N > 1); off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="cbf_qp: write the last timed step's outputs (rank 0) as DIR/<name>.npy, float32 / float64")
+    a = ap.parse_args()
+    if a.dump_outputs and a.workload != "cbf_qp":
+        ap.error("--dump-outputs is implemented for the default cbf_qp workload only")
+    return a
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per output tensor, floats in their own width (float32 / float64), integers as float64
+    (exact).  Over DUMP_LIMIT_BYTES in all, the same fixed, seeded sample of rows (first axis) is kept of every array and its row
+    indices go to DIR/sample_rows.npy."""
+    import numpy as np
+    host = {}
+    for name, t in arrays.items():
+        x = t.detach().cpu().numpy()
+        host[name] = x if x.dtype in (np.float32, np.float64) else x.astype(np.float64)
+        if not np.isfinite(host[name]).all():
+            raise SystemExit(f"--dump-outputs: {name} holds {int((~np.isfinite(host[name])).sum())} non-finite values")
+    total = sum(x.nbytes for x in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(host.values())).shape[0]
+        keep = max(1, int(n * DUMP_LIMIT_BYTES // (total + 8 * n)))
+        rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        host = {k: x[rows] for k, x in host.items()}
+        host["sample_rows"] = rows.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, x in host.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x))
 
 
 def cpu_baseline(X, u_ref, obs, seconds):
@@ -1307,12 +1350,15 @@ def main():
         dist.barrier()                                              # closing bracket; the job time is the MAX over ranks
     elapsed = sharding.max_over_ranks(t1 - t0, device=dev if backend == "nccl" else None)
     kernel_ms = e0.elapsed_time(e1) / a.steps                       # avg launch duration over the timed region
+    if a.dump_outputs and rank == 0:                                # out holds what the last timed step returned; u is NaN by contract
+        u_dump = torch.where((out[1] == 0)[:, None], out[0], torch.zeros_like(out[0]))    # where status != 0 (no solution): 0 there
+        dump_outputs(a.dump_outputs, {"u": u_dump, "status": out[1], "h": out[2]})
 
     st = out[1]
     n_opt = int((st == 0).sum().item())
-    # N > 1: the one collective of the design (RCCL all-gather of the agent states, BASELINE configs[3]) is measured in the
-    # same run, on every rank, so that a scaling sweep of the default command covers the exchange path as well
-    coll = kb_c3bf_workload(a, dev, ws, rank, backend, collect=True, steps_override=20) if ws > 1 else None
+    # N > 1 with --full: the one collective of the design (RCCL all-gather of the agent states, BASELINE configs[3]) is measured in
+    # the same run, on every rank, so that a scaling sweep of the full command covers the exchange path as well
+    coll = kb_c3bf_workload(a, dev, ws, rank, backend, collect=True, steps_override=20) if (ws > 1 and a.full) else None
     if rank == 0:
         total = B * ws * a.steps
         alg_bytes = (BYTES_IN_CBFQP(K, es) + BYTES_OUT_CBFQP(K, es)) * B
@@ -1336,6 +1382,7 @@ def main():
                          # rocprofv3 --kernel-trace the dependent graph nodes are dispatched one completion signal at a time:
                          # its per-dispatch figure is that period when the launch is shorter (profiles/README.md, round 2)
                          "timing": "hip_events_over_timed_region"},
+            "cpu_baseline": None,                                   # measured with --full
         }
         pmc = os.path.join(ROOT, "profiles", "pmc_traffic.json")
         if os.path.exists(pmc):
@@ -1345,13 +1392,13 @@ def main():
                 pass
         if coll is not None:
             res["collective_leg"] = coll
-        if ws == 1 and not a.no_sweep:
+        if a.full and ws == 1 and not a.no_sweep:
             res["sweep"] = sweep(ctl, dev, td, es, K)
             try:
                 res["pipelined_two_batches"] = pipelined_leg(ctl, dev, X, ur, ob, K, a.steps)
             except Exception as e:                               # stream-fork capture is an extra, never fatal to the headline
                 res["pipelined_two_batches"] = {"error": repr(e)[:200]}
-        if ws == 1 and not a.no_mpc:
+        if a.full and ws == 1 and not a.no_mpc:
             res["mpc_cbf"] = mpc_leg(dev, 4096, 8, 10, steps=3, warmup=1,
                                      cpu_seconds=0.0 if a.no_cpu_baseline else 6.0)
             res["od_mpc_cbf"] = od_mpc_leg(dev)
@@ -1396,7 +1443,7 @@ def main():
                     res["hetero_fleet"] = hetero_fleet_workload(a, dev, ws, rank, backend, collect=True)
             except Exception as e:
                 res["hetero_fleet"] = {"error": repr(e)[:200]}
-        if ws == 1 and not a.no_cpu_baseline:
+        if a.full and ws == 1 and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(X.double().cpu().numpy(), ur.double().cpu().numpy(),
                                                ob.double().cpu().numpy(), a.cpu_seconds)
         emit(res, ws)

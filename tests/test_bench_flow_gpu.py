@@ -7,6 +7,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -20,7 +21,7 @@ def last_json(out):
 
 
 def test_single_gpu_line_has_contract_fields():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "2", "--full",
                         "--cpu-seconds", "1", "--no-sweep"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = last_json(r.stdout)
@@ -51,6 +52,33 @@ def test_single_gpu_line_has_contract_fields():
     # limit of 100 rides along)
     assert d["vtol_mpc_cbf"]["optimal_fraction"] > 0.9 and d["vtol_mpc_cbf"]["value"] > 3e3 and d["vtol_mpc_cbf"]["limit_100_ms"] < 150
     assert d["od_vtol_ms_mpc_cbf"]["kernel_ms"] > 0 and d["kinematic_bicycle_c3bf_mpc_cbf"].get("inaccurate", 0.0) <= 0.03
+
+
+def test_plain_line_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline alone (no CPU baseline, sweep or extra legs); --dump-outputs writes the last timed
+    step's outputs, and two runs with the same arguments write the same arrays."""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append((last_json(r.stdout), d))
+    line = runs[0][0]
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f64"
+    assert line["unit"] == "solves/s" and line["higher_is_better"] is True and line["cpu_baseline"] is None
+    assert abs(line["value"] - 4096 * 7 / (line["ms_per_step"] * 7 / 1e3)) / line["value"] < 1e-6
+    assert not {"sweep", "mpc_cbf", "kb_c3bf", "hetero_fleet", "collective_leg"} & set(line)
+    shapes = {"u": (4096, 2), "status": (4096,), "h": (4096, 8)}
+    for name, shape in shapes.items():
+        a, b = (np.load(d / f"{name}.npy") for _, d in runs)
+        assert a.shape == shape and a.dtype in (np.float32, np.float64), name
+        assert np.isfinite(a).all(), name
+        np.testing.assert_array_equal(a, b)
+    st, u = np.load(runs[0][1] / "status.npy"), np.load(runs[0][1] / "u.npy")
+    assert ((st == 0).mean() > 0.5) and set(np.unique(st)) <= {0.0, 1.0, 2.0, 3.0}
+    assert (st != 0).any() and (u[st != 0] == 0).all() and (np.abs(u[st == 0]).max(axis=1) > 0).mean() > 0.5
+    assert sorted(p.name for p in runs[0][1].iterdir()) == sorted(f"{n}.npy" for n in shapes)
 
 
 def test_two_rank_flow_on_one_gpu():
@@ -87,7 +115,7 @@ def test_gpus_flag_starts_its_own_ranks():
     group saw.  (One GPU here, so the ranks share it and rendezvous over gloo.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["SC_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "2", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     d = last_json(r.stdout)

@@ -17,8 +17,9 @@ pytestmark = pytest.mark.skipif(shutil.which("g++") is None, reason="g++ not ava
 
 
 @pytest.fixture(scope="module")
-def host():
+def host(tmp_path_factory):
     import dbg_vtol_host as Dh
+    Dh.SO = str(tmp_path_factory.mktemp("vtol_host") / "libvtol_host.so")     # not the tool's fixed /tmp path: another user may own it
     return Dh, Dh.build()
 
 

@@ -28,13 +28,13 @@ for CFG in "1048576 8 f32 f32" "1048576 8 f32 f64"; do
   rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES --output-format csv -d $OUT -o sqa_$TAG -- python3 $R/tools/prof_cbfqp.py $CFG 4 > /dev/null 2>&1
   rocprofv3 --kernel-trace --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VMEM SQ_INST_LEVEL_VMEM GRBM_GUI_ACTIVE --output-format csv -d $OUT -o sqb_$TAG -- python3 $R/tools/prof_cbfqp.py $CFG 4 > /dev/null 2>&1
 done
-# 4b. the full default bench line (sweep, closed-loop rollout and MPC legs) under the kernel trace
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench_full -- python3 $R/bench.py --no-cpu-baseline > $OUT/bench_full_under_rocprof.json 2>/dev/null
-# 4c. instruction counts of every interior-point leg of the default line (VALU rooflines of bench.py: with_roofline)
-rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --output-format csv -d $OUT -o bench_full_sq -- python3 $R/bench.py --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
+# 4b. the full bench line (--full: sweep, closed-loop rollout and MPC legs) under the kernel trace
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o bench_full -- python3 $R/bench.py --full --no-cpu-baseline > $OUT/bench_full_under_rocprof.json 2>/dev/null
+# 4c. instruction counts of every interior-point leg of the full line (VALU rooflines of bench.py: with_roofline)
+rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU --output-format csv -d $OUT -o bench_full_sq -- python3 $R/bench.py --full --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
 # 4d. lane utilisation and the f64 instruction mix of the same legs (separate passes: the SQ counters of one pass are limited)
-rocprofv3 --kernel-trace --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES --output-format csv -d $OUT -o bench_full_lane -- python3 $R/bench.py --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
-rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 --output-format csv -d $OUT -o bench_full_flop -- python3 $R/bench.py --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc SQ_THREAD_CYCLES_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES --output-format csv -d $OUT -o bench_full_lane -- python3 $R/bench.py --full --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_FMA_F64 SQ_INSTS_VALU_ADD_F64 SQ_INSTS_VALU_MUL_F64 SQ_INSTS_VALU_TRANS_F64 SQ_INSTS_VALU_MFMA_MOPS_F64 --output-format csv -d $OUT -o bench_full_flop -- python3 $R/bench.py --full --no-cpu-baseline --no-sweep --no-limit100 > /dev/null 2>&1
 # 5. MPC-CBF kernel
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT -o mpc -- python3 $R/bench.py --workload mpc_cbf --steps 5 --warmup 1 > $OUT/mpc_under_rocprof.json 2>/dev/null
 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVE_CYCLES SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT --output-format csv -d $OUT -o mpc_sq -- python3 $R/bench.py --workload mpc_cbf --steps 2 --warmup 1 --no-limit100 --no-cpu-baseline > /dev/null 2>&1
