@@ -758,6 +758,30 @@ int sc_tracking_apply_batch(const sc_tracking_params* params, int64_t B, int32_t
                             const void* u, const int32_t* u_status, void* u_last,
                             int32_t* ret, int32_t* ret_step, void* stream);
 
+/* Fleet step: agents are each other's moving obstacles (BASELINE configs[3] as a closed loop).  ONE control step
+ * (LocalTrackingControllerDyn.control_step, dynamic_env/main.py:126-236) for the B_local agents of this rank, whose
+ * obstacle list is vstack(obs_table [M,7], its nb_rows [K_nb,7]): table rows first, then the neighbour rows in their
+ * distance order (ties break in that order).  nb_rows [B_local,K_nb,7] is what sc_neighbor_obstacles_batch_ws wrote from
+ * the all-gathered published states with neighbour_radius = the robot radius; its padding rows (radius 0) are not
+ * candidates.  Every row is a circle [x, y, r, vx, vy, 0, 0] (flag 0).  The collision tests use copies of all rows advanced by dt (main.py:54-58); when params->dyn_obs the
+ * table itself is advanced by dt afterwards on the same stream.  params->n_steps must be 1; ret_step records step_index.
+ * Models: DynamicUnicycle2D and the KinematicBicycle2D family (4 states, X[3] = speed); K_nb <= 32, M <= 32,
+ * M + K_nb <= 64, num_constraints <= 16.
+ * X, waypoints, n_wp, wp_index, state_machine, goal, u_last, ret, ret_step as in sc_tracking_rollout_batch.
+ * X_pub [B_local,4] out: the state this agent publishes for the next step, (x, y, theta, v), v = 0 once ret != 0.
+ * cause [B_local] in/out: 0 none, 1 QP not optimal (degenerate rows included), 2 collision; set when ret turns -2.
+ * min_sep [B_local] in/out (io_dtype; start at +inf): running minimum, over the steps the agent ran, of the distance
+ * to its nearest other agent (neighbour row 0) minus twice the robot radius.
+ */
+int sc_tracking_fleet_step_batch(const sc_tracking_params* params, int64_t B_local, int32_t M, int32_t K_nb,
+                                 int32_t step_index, void* X, void* X_pub, const void* waypoints, const int32_t* n_wp,
+                                 int32_t* wp_index, int32_t* state_machine, void* goal, void* obs_table,
+                                 const void* nb_rows, void* u_last, int32_t* ret, int32_t* ret_step, int32_t* cause,
+                                 void* min_sep, void* stream);
+#define SC_FLEET_MAX_NEIGHBOURS 32
+#define SC_FLEET_MAX_TABLE      32
+#define SC_FLEET_MAX_ROWS       64   /* M + K_nb */
+
 /* Closed loop for the arm (SURVEY 8f-1 for Manipulator2D): `n_steps` iterations of LocalTrackingController.control_step
  * (tracking.py:559-668; goal_reached on the end effector :263-268; update_goal :497-535) with nominal_input / step of
  * robots/manipulator2D.py:38-41,110-127 and the CBF-QP above, one arm per wavefront, joint angles in registers.

@@ -20,6 +20,6 @@ from .position_control.optimal_decay_cbf_qp import OptimalDecayCBFQP, BatchedOpt
 from .position_control.optimal_decay_mpc_cbf import OptimalDecayMPCCBF, BatchedOptimalDecayMPCCBF  # noqa: F401
 from .position_control.optimal_decay_mpc_cbf_gn import OptimalDecayGnMPCCBF, BatchedOptimalDecayGnMPCCBF  # noqa: F401
 from .robots.spec import RobotHandle, complete_robot_spec  # noqa: F401
-from .tracking import BatchedTrackingController  # noqa: F401
+from .tracking import BatchedTrackingController, BatchedFleetTrackingController  # noqa: F401
 
 __version__ = "0.1.0"

@@ -38,6 +38,9 @@ hipError_t tracking_apply_launch(const sc_tracking_params& p, long long B, int M
 hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                            int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                            void* tX, void* tU, hipStream_t stream);
+hipError_t tracking_fleet_launch(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
+                                 const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, void* table,
+                                 const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream);
 
 hipError_t manip_cbfqp_launch(const sc_manip_cbfqp_params& p, long long B, int K, const void* X, const void* u_ref,
                               const void* obs, const int* n_obs, void* u_out, int* status, void* h_out, hipStream_t stream);
@@ -1295,6 +1298,42 @@ int sc_tracking_apply_batch(const sc_tracking_params* params, int64_t B, int32_t
     hipError_t e = sc::tracking_apply_launch(*params, (long long)B, (int)M, (int)step_index, X, state_machine, goal, obs_table,
                                              u, u_status, u_last, ret, ret_step, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "tracking apply kernel launch");
+    return SC_OK;
+}
+
+int sc_tracking_fleet_step_batch(const sc_tracking_params* params, int64_t B_local, int32_t M, int32_t K_nb, int32_t step_index,
+                                 void* X, void* X_pub, const void* waypoints, const int32_t* n_wp, int32_t* wp_index,
+                                 int32_t* state_machine, void* goal, void* obs_table, const void* nb_rows, void* u_last,
+                                 int32_t* ret, int32_t* ret_step, int32_t* cause, void* min_sep, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    const sc_cbfqp_params* q = &params->qp;
+    if (B_local < 0 || M < 0 || K_nb < 0 || step_index < 0)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "B_local, M, K_nb and step_index must be >= 0");
+    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && q->model_id != SC_MODEL_KINEMATIC_BICYCLE2D &&
+        q->model_id != SC_MODEL_KINEMATIC_BICYCLE2D_C3BF && q->model_id != SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF)
+        return sc::fail(SC_ERR_UNSUPPORTED, "the fleet step is built for DynamicUnicycle2D and the KinematicBicycle2D family");
+    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (params->num_constraints < 1 || params->num_constraints > SC_TRACKING_MAX_CONSTRAINTS)
+        return sc::fail(SC_ERR_UNSUPPORTED, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
+    if (K_nb > SC_FLEET_MAX_NEIGHBOURS) return sc::fail(SC_ERR_UNSUPPORTED, "K_nb exceeds SC_FLEET_MAX_NEIGHBOURS");
+    if (M > SC_FLEET_MAX_TABLE) return sc::fail(SC_ERR_UNSUPPORTED, "M exceeds SC_FLEET_MAX_TABLE");
+    if (M + K_nb > SC_FLEET_MAX_ROWS) return sc::fail(SC_ERR_UNSUPPORTED, "M + K_nb exceeds SC_FLEET_MAX_ROWS");
+    if (params->n_steps != 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "the fleet step runs one control step per call: n_steps must be 1");
+    if (params->max_waypoints < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "max_waypoints < 1");
+    if (!(q->dt > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0");
+    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && (!(q->rear_ax_dist > 0) || !(params->wheel_base > 0)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "rear_ax_dist and wheel_base must be > 0 for the KinematicBicycle2D family");
+    if (B_local > 0 && (!X || !X_pub || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !u_last || !ret || !ret_step ||
+                        !cause || !min_sep || (M > 0 && !obs_table) || (K_nb > 0 && !nb_rows)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B_local == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_fleet_launch(*params, (long long)B_local, (int)M, (int)K_nb, (int)step_index, X, X_pub, waypoints, n_wp,
+                                             wp_index, state_machine, goal, obs_table, nb_rows, u_last, ret, ret_step, cause, min_sep,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "tracking fleet kernel launch");
     return SC_OK;
 }
 

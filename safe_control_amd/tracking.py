@@ -575,3 +575,119 @@ class BatchedQuadTrackingController(BatchedTrackingController):
                 tU[k] = self.u_pos
         self.steps_done += n
         return (self.ret, tX, tU) if record else self.ret
+
+
+class BatchedFleetTrackingController(BatchedTrackingController):
+    """A fleet whose agents are each other's moving obstacles (BASELINE configs[3] as a closed loop).
+
+    Every agent runs ``LocalTrackingControllerDyn.control_step`` (dynamic_env/main.py:126-236) against
+    ``vstack(T, N_i)``: the shared moving-obstacle table ``obs`` (``T``, M rows, may be empty) and its
+    ``neighbours`` (K_nb) nearest other agents, which the neighbour kernel builds from the states the fleet
+    published at the start of the step (``[x, y, r, v cos th, v sin th, 0, 0]`` with r = the robot radius;
+    a frozen agent publishes v = 0 and stays in the fleet as a stationary obstacle).
+
+    ``X0`` is the WHOLE fleet; under ``torch.distributed`` each rank keeps its ``sharding.agent_range``
+    shard and a step is one all-gather of the published states (``sharding.NeighborExchange``) plus the
+    fused fleet kernel (csrc/tracking.hip).  ``set_waypoints`` takes the whole fleet's lists (or one
+    shared list).  Besides ``ret`` / ``ret_step`` every agent keeps ``cause`` (0 none, 1 QP not optimal,
+    2 collision) and ``min_sep`` (running minimum of the distance to its nearest other agent minus 2 R).
+    Models: DynamicUnicycle2D and the KinematicBicycle2D family; position controller 'cbf_qp'.
+    """
+
+    MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF")
+
+    def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, dyn_obs=False,
+                 neighbours=16, num_constraints=None, io_dtype="f64", device="cuda:0"):
+        from . import sharding
+        robot_spec = dict(robot_spec)
+        if robot_spec.get("model", "DynamicUnicycle2D") not in self.MODELS:
+            raise ValueError(f"the fleet step supports {', '.join(self.MODELS)}; not {robot_spec.get('model')!r}")
+        if (controller_type or {"pos": "cbf_qp"}).get("pos", "cbf_qp") != "cbf_qp":
+            raise ValueError("the fleet step's position controller is 'cbf_qp'")
+        if num_constraints is not None:
+            robot_spec["num_constraints"] = int(num_constraints)
+        K = int(neighbours)
+        M = 0 if obs is None else len(obs)
+        nc = int(robot_spec.get("num_constraints", 10))
+        if not 0 <= K <= _lib.FLEET_MAX_NEIGHBOURS:
+            raise ValueError(f"neighbours must be in [0, {_lib.FLEET_MAX_NEIGHBOURS}]")
+        if M > _lib.FLEET_MAX_TABLE or M + K > _lib.FLEET_MAX_ROWS:
+            raise ValueError(f"obstacle table of {M} rows: at most {_lib.FLEET_MAX_TABLE}, and at most {_lib.FLEET_MAX_ROWS} with the neighbours")
+        if not 1 <= nc <= 16:
+            raise ValueError("num_constraints must be in [1, 16]")
+        X0 = np.asarray(X0, dtype=np.float64)
+        if X0.ndim == 1:
+            X0 = X0[None, :]
+        self.n_agents = X0.shape[0]
+        self.ws, self.rank = sharding.world()
+        self.lo, self.hi = sharding.agent_range(self.n_agents, self.ws, self.rank)
+        if M and np.asarray(obs, dtype=np.float64).shape[1] >= 7 and np.any(np.asarray(obs, dtype=np.float64)[:, 6] != 0):
+            raise ValueError("the fleet's obstacle table holds moving circles [x, y, r, vx, vy, 0, 0] only")
+        super().__init__(X0[self.lo:self.hi], robot_spec, controller_type={"pos": "cbf_qp"}, dt=dt,
+                         enable_rotation=enable_rotation, obs=obs, dyn_obs=dyn_obs, io_dtype=io_dtype, device=device)
+        torch = self.torch
+        self.neighbours = K
+        self.neighbour_radius = float(self.robot_spec["radius"])
+        self.exchange = sharding.NeighborExchange(self.n_agents, K, self.neighbour_radius, nx=4, dtype=self.tdtype,
+                                                  device=self.device) if K > 0 else None
+        self.X_pub = self.X.clone()
+        self.cause = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.min_sep = torch.full((self.B,), math.inf, dtype=self.tdtype, device=self.device)
+
+    def set_waypoints(self, waypoints):
+        """The whole fleet's waypoint lists (or one list shared by every agent); resets the return codes and records."""
+        shared = (isinstance(waypoints, np.ndarray) and waypoints.ndim == 2) or \
+            (isinstance(waypoints, (list, tuple)) and len(waypoints) > 0 and np.ndim(waypoints[0]) == 1)
+        if not shared:
+            if len(waypoints) != self.n_agents:
+                raise ValueError(f"one waypoint list per agent of the fleet ({self.n_agents}) expected")
+            waypoints = list(waypoints[self.lo:self.hi])
+        super().set_waypoints(waypoints)
+        self.X_pub.copy_(self.X)
+        self.cause.zero_()
+        self.min_sep.fill_(math.inf)
+
+    def control_step(self, n=1, record=False):
+        """``n`` fleet steps, each = all-gather of the published states + neighbour search + one fleet launch (stream-ordered,
+        no host sync).  Returns ``ret`` [B_local] (and ``(traj_X [n,B_local,4], traj_U [n,B_local,2])`` when ``record``)."""
+        torch = self.torch
+        if self.waypoints is None:
+            raise RuntimeError("call set_waypoints first")
+        p = self._params(1)
+        M, K = int(self.obs.shape[0]), self.neighbours
+        tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
+        tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        obs_ptr = self.obs.data_ptr() if M else None
+        for k in range(n):
+            nb = self.exchange.step(self.X_pub) if K > 0 else None
+            rc = self._lib.sc_tracking_fleet_step_batch(
+                C.byref(p), self.B, M, K, self.steps_done + k, self.X.data_ptr(), self.X_pub.data_ptr(),
+                self.waypoints.data_ptr(), self.n_wp.data_ptr(), self.current_goal_index.data_ptr(),
+                self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr, nb.data_ptr() if nb is not None else None,
+                self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), self.cause.data_ptr(),
+                self.min_sep.data_ptr(), stream)
+            _lib.check(rc, "sc_tracking_fleet_step_batch")
+            if record:
+                tX[k] = self.X
+                tU[k] = self.u_pos
+        self.steps_done += n
+        return (self.ret, tX, tU) if record else self.ret
+
+    def summary(self):
+        """Fleet-wide counts and the smallest separation: dict(agents, running, reached, infeasible, collided, min_sep).
+        One all_reduce per quantity when sharded, one host sync."""
+        torch = self.torch
+        from . import sharding
+        r, c = self.ret, self.cause
+        counts = torch.stack([(r == 0).sum(), (r == -1).sum(), ((r == -2) & (c == 1)).sum(), ((r == -2) & (c == 2)).sum()])
+        msep = self.min_sep.double().min().reshape(1) if self.B else torch.full((1,), math.inf, dtype=torch.float64, device=self.device)
+        if self.ws > 1:
+            import torch.distributed as dist
+            host = dist.get_backend() == "gloo"                    # gloo reduces host tensors
+            counts, msep = (counts.cpu(), msep.cpu()) if host else (counts, msep)
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM)
+            dist.all_reduce(msep, op=dist.ReduceOp.MIN)
+        v = torch.cat([counts.double(), msep.to(counts.device)]).cpu().tolist()
+        return {"agents": self.n_agents, "running": int(v[0]), "reached": int(v[1]), "infeasible": int(v[2]),
+                "collided": int(v[3]), "min_sep": float(v[4])}

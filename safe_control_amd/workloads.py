@@ -191,3 +191,41 @@ def superellipsoid_obstacles(pos, K=8, seed=0, radius=0.25, exponents=(4.0, 6.0)
     obs[..., 1] = pos[:, None, 1] + rho * np.sin(phi)
     obs[..., 2], obs[..., 3], obs[..., 4], obs[..., 5], obs[..., 6] = a, b, e, th, 1.0
     return obs
+
+
+def kb_c3bf_fleet_scene(n_agents, n_moving=16, seed=0, spec=None, spacing=3.0, goal_dist=(10.0, 20.0)):
+    """BASELINE configs[3] as a closed loop (BatchedFleetTrackingController): a fleet of KinematicBicycle2D C3BF agents
+    that are each other's moving obstacles, plus a table of moving circles.
+
+    Agents sit on a square grid ``spacing`` m apart (the bench leg's ~3 m mean spacing), jittered by up to 0.15 spacing,
+    so everyone starts clear of everyone else; each is headed at its one waypoint, ``goal_dist`` m away in a random
+    direction, with a start speed in [0.5, 1.5] m/s (no C3BF row starts degenerate).  The table holds ``n_moving``
+    r = 0.5 circles with velocities in [-0.5, 0.5] m/s (dynamic_env/main.py:248-268), placed clear of every agent.
+    Returns float64 X0 [n,4], waypoints [n,1,2], obs [n_moving,7].
+    """
+    from .robots.spec import complete_robot_spec
+    spec = complete_robot_spec(dict(spec or {"model": "KinematicBicycle2D_C3BF"}))
+    R = spec["radius"]
+    rng = np.random.default_rng(seed)
+    side = int(math.ceil(math.sqrt(n_agents)))
+    gi = np.arange(n_agents)
+    X0 = np.empty((n_agents, 4))
+    X0[:, 0] = (gi % side) * spacing + rng.uniform(-0.15, 0.15, n_agents) * spacing
+    X0[:, 1] = (gi // side) * spacing + rng.uniform(-0.15, 0.15, n_agents) * spacing
+    phi = rng.uniform(-np.pi, np.pi, n_agents)
+    d = rng.uniform(goal_dist[0], goal_dist[1], n_agents)
+    X0[:, 2] = phi
+    X0[:, 3] = rng.uniform(0.5, 1.5, n_agents)
+    wps = np.stack([X0[:, 0] + d * np.cos(phi), X0[:, 1] + d * np.sin(phi)], axis=1)[:, None, :]
+    obs = np.zeros((n_moving, 7))
+    ext = side * spacing
+    k = 0
+    while k < n_moving:                                       # rejection: at least 0.5 + R + 0.3 m from every agent
+        c = rng.uniform(-0.5 * spacing, ext - 0.5 * spacing, 2)
+        if np.min(np.hypot(X0[:, 0] - c[0], X0[:, 1] - c[1])) < 0.5 + R + 0.3:
+            continue
+        obs[k, 0:2] = c
+        obs[k, 2] = 0.5
+        obs[k, 3:5] = rng.uniform(-0.5, 0.5, 2)
+        k += 1
+    return X0, wps, obs
