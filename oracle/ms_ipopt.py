@@ -591,7 +591,10 @@ OPTS = dict(tol=1e-8, max_iter=3000, dual_inf_tol=1.0, constr_viol_tol=1e-4, com
             # running out of iterations: status 2) -- the iterate is the optimum, what does not come down is the precision floor of the multiplier
             # recovery (DESIGN.md kernel 12), and IPOPT itself would spend the rest of its 3000 iterations there for the same input (0: never)
             floor_iter=0,
-            filter_cap=0)                   # (experiments: emulate a kernel's fixed-size filters; 0 = unbounded, as IPOPT's)
+            filter_cap=0,                   # (experiments: emulate a kernel's fixed-size filters; 0 = unbounded, as IPOPT's)
+            # what a full filter does (filter_cap > 0): "overwrite" its last entry and go on (csrc/mpc_vtol_ms.hip), or "stop" the solve at the
+            # next iterate with status 2, in either phase (kernel 13: csrc/mpc_du_ms_solver.hpp filter_add / the filt_over test at the loop's top)
+            filter_overflow="overwrite")
 
 EPS = np.finfo(float).eps
 
@@ -687,6 +690,8 @@ class _Resto(_Problem):
 # what csrc/mpc_vtol_ms.hip runs (DESIGN.md kernel 12): stage-wise Riccati linear algebra, no second-order corrections, restoration phase with
 # elastic variables on the inequality rows only, the stall rule, the precision-floor stop.  KERNEL_PROFILE_NO_RESTO: the same without a restoration phase (status 4).
 KERNEL_PROFILE = dict(linear_solver="riccati", max_soc=0, resto_elastic="ineq", stall_iter=60, stall_alpha=1e-4, floor_iter=30)
+# KERNEL13_PROFILE: kernel 13 (csrc/mpc_du_ms_solver.hpp), whose 128-entry filters end a solve 'inaccurate' when they run over.
+KERNEL13_PROFILE = dict(KERNEL_PROFILE, filter_cap=128, filter_overflow="stop")
 KERNEL_PROFILE_NO_RESTO = dict(linear_solver="riccati", max_soc=0, restoration="none", stall_iter=60, stall_alpha=1e-4, floor_iter=30)
 
 
@@ -703,9 +708,11 @@ def _ftb(tau, slack, dslack):
 
 
 class _Filter:
-    def __init__(self, cap=0):
+    def __init__(self, cap=0, overflow="overwrite"):
         self.e = []
-        self.cap = cap          # > 0: a kernel's fixed-size filter -- a full filter overwrites its last entry (option filter_cap; experiments only)
+        self.cap = cap          # > 0: a kernel's fixed-size filter -- a full filter overwrites its last entry (option filter_cap)
+        self.stop = overflow == "stop"      # ... and, with filter_overflow = "stop", marks the solve to end (kernel 13)
+        self.full = False
         self.peak = 0
 
     def acceptable(self, phi, theta):
@@ -716,8 +723,9 @@ class _Filter:
 
     def add(self, phi, theta):
         self.e = [(p, t) for (p, t) in self.e if not (p >= phi and t >= theta)]
-        if self.cap > 0 and len(self.e) >= self.cap:
+        if self.cap > 0 and len(self.e) >= self.cap:             # (the size test after the pruning, as the kernels')
             self.e = self.e[:self.cap - 1]
+            self.full = self.full or self.stop
         self.e.append((phi, theta))
         self.peak = max(self.peak, len(self.e))
 
@@ -731,9 +739,13 @@ class _Algo:
     def __init__(self, prob, o, resto_of=None, trace=None):
         self.P, self.o, self.outer, self.trace = prob, o, resto_of, trace
         self.in_resto = resto_of is not None
-        self.filter = _Filter(int(o.get("filter_cap", 0) or 0))
+        self.filter = _Filter(int(o.get("filter_cap", 0) or 0), o.get("filter_overflow", "overwrite"))
         self.delta_w_last = 0.0
         self.iters = 0
+        self.exit = "error"             # the rule that ended run(): see EXITS
+        self.resto_peak = 0             # largest filter of the restoration phases this run entered
+        self.n_resto = 0                # restoration phases entered, and the iterations spent in them
+        self.resto_iters = 0
 
     # -- quantities of an iterate --------------------------------------------------------------------------------------
     def slacks(self, x, t):
@@ -1175,6 +1187,9 @@ class _Algo:
         first_iter = True
         status = "max_iter"
         while True:
+            if self.filter.full:                                            # (kernel 13 tests this before it evaluates the iterate)
+                status, self.exit = "filter_full", "filter_full"
+                break
             E0, dinf, pinf, comp, r = self.errors(ev, x, t, y, z, 0.0)
             if self.trace is not None:
                 self.trace.append(dict(it=self.total_iters(), resto=self.in_resto, E0=E0, dinf=dinf, pinf=pinf, comp=comp, mu=mu, f=ev["f"],
@@ -1183,24 +1198,24 @@ class _Algo:
             if self.in_resto:
                 st = self.outer_progress(x, t, first_iter)
                 if st:
-                    status = "orig_progress"
+                    status, self.exit = "orig_progress", "orig_progress"
                     break
             df = getattr(P, "df", 1.0)
             dgs = getattr(P, "dg", None)
             un_pinf = float(np.max(np.abs(r / dgs), initial=0.0)) if dgs is not None else pinf
             if E0 <= o["tol"] and dinf / df <= o["dual_inf_tol"] and un_pinf <= o["constr_viol_tol"] and comp / df <= o["compl_inf_tol"]:
-                status = "optimal"
+                status, self.exit = "optimal", "tol"
                 break
             if E0 <= o["acceptable_tol"] and dinf / df <= o["acceptable_dual_inf_tol"] and un_pinf <= o["acceptable_constr_viol_tol"] \
                     and comp / df <= o["acceptable_compl_inf_tol"]:
                 n_acc += 1
                 if n_acc >= o["acceptable_iter"]:
-                    status = "acceptable"
+                    status, self.exit = "acceptable", "acceptable"
                     break
             else:
                 n_acc = 0
             if self.total_iters() >= budget:
-                status = "max_iter"
+                status, self.exit = "max_iter", "max_iter"
                 break
             if not self.in_resto and o["recalc_y_iter"] > 0 and not getattr(self, "recalc_y", False):
                 sxL_, sxU_, stL_, stU_ = self.slacks(x, t)
@@ -1223,10 +1238,11 @@ class _Algo:
                             and comp <= o["acceptable_compl_inf_tol"] * df)
                 self.n_at_floor = getattr(self, "n_at_floor", 0) + 1 if at_floor else 0
                 if self.n_at_floor >= o["floor_iter"]:
-                    status = "max_iter"
+                    status, self.exit = "max_iter", "floor"
                     break
             if o["stall_iter"] > 0 and getattr(self, "n_tiny", 0) >= o["stall_iter"]:
                 status = "resto_failed" if self.in_resto else "max_iter"     # (the stall rule, in either phase: same class as running out of iterations)
+                self.exit = "stall"
                 break
             # ---- barrier parameter -----------------------------------------------------------------------------------------
             mu_min = min(o["tol"], o["compl_inf_tol"]) / (o["barrier_tol_factor"] + 1.0)
@@ -1271,15 +1287,15 @@ class _Algo:
                 need_resto = acc is None
             if need_resto:
                 if self.in_resto:
-                    status = "resto_failed"
+                    status, self.exit = "resto_failed", "resto_failed"
                     break
                 if o.get("restoration", "ipopt") == "none":               # the caller has another solver for these (csrc/mpc_vtol_ms.hip: the
-                    status = "needs_resto"                                  # condensed wave kernel and its restoration)
+                    status, self.exit = "needs_resto", "needs_resto"        # condensed wave kernel and its restoration)
                     break
                 rs = self.restoration(x, t, y, z, mu, ev, budget)
                 self.n_tiny = 0
                 if rs[0] != "ok":
-                    status, x, t = rs[0], rs[1], rs[2]
+                    status, x, t, self.exit = rs[0], rs[1], rs[2], rs[3]
                     ev = P.evaluate(x, 2, mu)
                     break
                 _, x, t, z = rs
@@ -1402,10 +1418,13 @@ class _Algo:
         P, o = self.P, self.o
         r = self.residual(ev["g"], t)
         if float(np.max(np.abs(r), initial=0.0)) <= o["resto_failure_feasibility_threshold"]:
-            return ("resto_failed", x, t)                                   # "restoration phase is called at a point that is almost feasible"
+            return ("resto_failed", x, t, "resto_failed")                   # "restoration phase is called at a point that is almost feasible"
         theta = float(np.sum(np.abs(r)))
         phi = self.barrier(ev["f"], x, t, mu)
         self.filter.add(phi - o["gamma_phi"] * theta, (1.0 - o["gamma_theta"]) * theta)
+        if self.filter.full:                                                # (kernel 13: the entry's add ran over; it stops before the first restoration iterate)
+            return ("filter_full", x, t, "filter_full")
+        self.n_resto += 1
         RP = _Resto(P, x, o)
         ra = _Algo(RP, o, resto_of=self, trace=self.trace)
         ra.orig = dict(mu=mu, theta=theta, phi=phi, pinf=float(np.max(np.abs(r))))
@@ -1424,6 +1443,8 @@ class _Algo:
         zr = tuple(np.where(np.isfinite(s_), z_, 0.0) for z_, s_ in zip(zr, ra.slacks(x, tt)))
         st, xr, tr, yr, zrr, mur = ra.run(x.copy(), tt, np.zeros(P.m), zr, mu_r, budget)
         self.iters += ra.iters
+        self.resto_iters += ra.iters
+        self.resto_peak = max(self.resto_peak, ra.filter.peak)
         ra.outer = None
         ns = P.nt
         if st == "orig_progress":
@@ -1435,8 +1456,8 @@ class _Algo:
         if st in ("optimal", "acceptable"):
             rr = self.residual(P.evaluate(xr, 0, mu)["g"], tr[:ns])
             feas = float(np.max(np.abs(rr), initial=0.0)) <= 1e2 * o["tol"]
-            return ("resto_converged_feasible" if feas else "local_infeasibility", xr, tr[:ns])
-        return (st if st == "max_iter" else "resto_failed", xr, tr[:ns])
+            return ("resto_converged_feasible" if feas else "local_infeasibility", xr, tr[:ns], "resto_failed" if feas else "infeasible")
+        return (st if st in ("max_iter", "filter_full") else "resto_failed", xr, tr[:ns], ra.exit)
 
     def outer_progress(self, x, tt, first_iter):
         """RestoFilterConvergenceCheck: leave the restoration when the (x, s) part is acceptable to the original filter and to the
@@ -1460,7 +1481,12 @@ class _Algo:
         return out.acceptable_to_iterate(phi_t, th_t, self.orig["phi"], self.orig["theta"])
 
 
-STATUS_OF = dict(optimal=0, acceptable=0, local_infeasibility=1, max_iter=2, resto_failed=2, resto_converged_feasible=2, error=2, needs_resto=4)
+STATUS_OF = dict(optimal=0, acceptable=0, local_infeasibility=1, max_iter=2, resto_failed=2, resto_converged_feasible=2, filter_full=2, error=2, needs_resto=4)
+# info["exit"]: the rule that ended a solve.  tol / acceptable: IPOPT's convergence tests (status 0); infeasible: the restoration phase's
+# certificate (status 1); max_iter: the iteration budget; stall / floor / filter_full: the kernels' own exits (options stall_iter, floor_iter,
+# filter_cap with filter_overflow = "stop"; status 2); resto_failed: a restoration phase that failed or ended at a feasible point (status 2);
+# needs_resto: restoration = "none" (status 4); error: none of these.
+EXITS = ("tol", "acceptable", "infeasible", "max_iter", "stall", "floor", "filter_full", "resto_failed", "needs_resto", "error")
 
 
 def solve_nlp(nlp, w0, opts=None, trace=None):
@@ -1491,7 +1517,8 @@ def _solve_nlp(nlp, w0, opts, trace):
     status, x, s, y, z, mu = A.run(x, s, y, z, o["mu_init"], o["max_iter"])
     ev = nlp.evaluate(x, 0)
     return dict(x=x, status=status, code=STATUS_OF.get(status, 2), iters=A.iters, f=ev["f"], c=ev["c"], d=ev["d"], y=y,
-                mu=mu, obj_scale=P.df, con_scale=P.dg)
+                mu=mu, obj_scale=P.df, con_scale=P.dg, exit=A.exit if A.exit in EXITS else "error",
+                filter_peak=max(A.filter.peak, A.resto_peak), n_resto=A.n_resto, resto_iters=A.resto_iters)
 
 
 def solve(model, x0, u_prev, goal, obs, N=None, opts=None, return_info=False, trace=None):

@@ -1,6 +1,7 @@
 """Runs the numpy MPC oracle over a whole batch on the host cores: plain child processes (``python tests/_oracle_pool.py
 in.npz out.npz``), one slice of the batch each, so nothing depends on fork/spawn semantics of a parent that may hold a HIP
-context.  Test infrastructure only."""
+context.  At most MAX_WORKERS of them at a time.  Test infrastructure only."""
+import json
 import os
 import subprocess
 import sys
@@ -9,6 +10,107 @@ import tempfile
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+MAX_WORKERS = 16                    # worker processes per batch, by default and at most
+TRACE_ROWS = 16                     # iterate-trace rows kept per multiple-shooting solve
+
+
+# ---- oracle/ms_ipopt.py (kernels 12 and 13) -----------------------------------------------------------------------------------
+MS_FAMILIES = {"du": "DynamicUnicycle2D", "uni": "Unicycle2D", "di": "DoubleIntegrator2D", "si": "SingleIntegrator2D",
+               "kb": "KinematicBicycle2D", "vtol": "VTOL2D", "vtol_od": "VTOL2D"}
+
+
+def ms_model(family, spec=None):
+    """The oracle model of `family` built from the completed robot_spec the kernel gets (safe_control_amd.robots.spec), not from the
+    model's own defaults: every limit and radius is the host class's."""
+    from oracle import ms_ipopt as MS
+    from safe_control_amd.robots.spec import complete_robot_spec
+    mk = {"du": MS.du_model, "uni": MS.uni_model, "di": MS.di_model, "si": MS.si_model, "kb": MS.kb_model,
+          "vtol": MS.vtol_model, "vtol_od": MS.vtol_od_model}[family]
+    sp = complete_robot_spec(dict(spec or {}, model=MS_FAMILIES[family]))
+    keys = mk()["spec"].keys()
+    return mk({k: v for k, v in sp.items() if k in keys})
+
+
+def _worker_ms(d, outp):
+    """kind = "ms:<family>": oracle.ms_ipopt.solve with params dict(opts=<profile>, N=<horizon or None>, spec=<robot_spec>); per row
+    u, st, it, plan (X then U, flattened), exit (index into ms_ipopt.EXITS), filter_peak, resto (restoration phases entered),
+    resto_iters, f, and the first TRACE_ROWS rows of the iterate trace [E0, dinf, pinf, comp, mu, theta, delta_w, alpha] (NaN past
+    the end; ntr rows in all; the restoration's rows carry -alpha and resto_row = 1)."""
+    from oracle import ms_ipopt as MS
+    fam = str(d["kind"])[3:]
+    X, up, goal, obs = d["X"], d["up"], d["goal"], d["obs"]
+    prm = d["params"].item() if "params" in d.files else {}
+    prm = dict(prm or {})
+    mdl = ms_model(fam, prm.get("spec"))
+    opts, N = dict(prm.get("opts") or MS.KERNEL_PROFILE), prm.get("N")
+    B = X.shape[0]
+    out = {k: [] for k in ("u", "st", "it", "plan", "exit", "filter_peak", "resto", "resto_iters", "f", "trace", "resto_row", "ntr")}
+    for i in range(B):
+        tr = []
+        u, st, it, info = MS.solve(mdl, X[i], up[i], goal[i], obs[i] if obs.ndim == 3 else obs, N=N, return_info=True, opts=opts, trace=tr)
+        T = np.full((TRACE_ROWS, 8), np.nan)
+        rr = np.zeros(TRACE_ROWS, dtype=np.int64)
+        for j, q in enumerate(tr[:TRACE_ROWS]):
+            T[j] = [q["E0"], q["dinf"], q["pinf"], q["comp"], q["mu"], q["theta"], q["delta"], -q["alpha"] if q["resto"] else q["alpha"]]
+            rr[j] = int(q["resto"])
+        for k, v in (("u", u), ("st", st), ("it", it), ("plan", np.concatenate([info["X"].reshape(-1), info["U"].reshape(-1)])),
+                     ("exit", MS.EXITS.index(info["exit"])), ("filter_peak", info["filter_peak"]), ("resto", info["n_resto"]),
+                     ("resto_iters", info["resto_iters"]), ("f", info["f"]), ("trace", T), ("resto_row", rr), ("ntr", len(tr))):
+            out[k].append(v)
+    np.savez(outp, **{k: np.array(v) for k, v in out.items()})
+
+
+def ms_solve_many(family, X, up, goal, obs, opts=None, N=None, spec=None, workers=None, timeout=1800):
+    """oracle.ms_ipopt.solve with the model of `family` (ms_model) on every row (obs [B,K,7] or one shared [K,7] table); dict of
+    arrays, see _worker_ms; exit as the names of ms_ipopt.EXITS."""
+    from oracle import ms_ipopt as MS
+    B = X.shape[0]
+    ob = obs if obs.ndim == 3 else np.broadcast_to(obs, (B,) + obs.shape)
+    r = _run(dict(kind=np.array("ms:" + family)), X, up, goal, np.ascontiguousarray(ob), dict(opts=opts, N=N, spec=spec), workers, timeout)
+    r["exit"] = np.array(MS.EXITS)[r["exit"]]
+    return r
+
+
+_CACHE = {}
+
+
+def _key(family, tag, opts, N, spec):
+    from oracle import ms_ipopt as MS
+    mdl = ms_model(family, spec)                                  # (the model's numbers: two ways of writing one robot_spec share a run)
+    return (family, json.dumps(tag, sort_keys=True), json.dumps(dict(opts or MS.KERNEL_PROFILE), sort_keys=True), N,
+            json.dumps(mdl["spec"], sort_keys=True, default=repr))
+
+
+def ms_cached(family, tag, X, up, goal, obs, opts=None, N=None, spec=None):
+    """ms_solve_many, solved once per test session for each (family, tag, options): `tag` names the inputs (the generator, its seed
+    and batch size), so that every test that reads the same problems reads one oracle run."""
+    k = _key(family, tag, opts, N, spec)
+    if k not in _CACHE:
+        _CACHE[k] = ms_solve_many(family, X, up, goal, obs, opts=opts, N=N, spec=spec)
+    return _CACHE[k]
+
+
+def ms_batch(family, seed=0, B=4096, K=8, opts=None, N=None, spec=None):
+    """workloads.mpc_family_batch(family, B, K, seed) and the oracle's solve of every problem of it (cached per session):
+    ((X, up, goal, obs), dict of arrays)."""
+    from safe_control_amd import workloads as W
+    X, up, goal, obs = W.mpc_family_batch(family, B, K, seed=seed)
+    return (X, up, goal, obs), ms_cached(family, ("mpc_family_batch", seed, B, K), X, up, goal, obs, opts=opts, N=N, spec=spec)
+
+
+def mixed_scene(fam, n, seed=3):
+    """The first n problems of the seed-0 bench batch of `fam` with ~60 % of their obstacle rows replaced by superellipsoids."""
+    from safe_control_amd import workloads as W
+    X, up, goal, obs = (a[:n].copy() for a in W.mpc_family_batch(fam, 4096, 8, seed=0))
+    se = W.superellipsoid_obstacles(X[:, :2], 8, seed=seed, radius=0.25, rho_max=2.5)
+    mix = np.random.default_rng(1).random((n, 8)) < 0.6
+    obs[mix] = se[mix]
+    return X, up, goal, obs
+
+
+def take(res, idx):
+    """Rows `idx` of a result dict."""
+    return {k: v[idx] for k, v in res.items()}
 
 
 def _worker_od_rd1(d, outp):
@@ -131,6 +233,8 @@ def _worker(inp, outp):
         return _worker_phase1(d, outp)
     if "kind" in d.files and str(d["kind"]).startswith("fam:"):
         return _worker_family(d, outp)
+    if "kind" in d.files and str(d["kind"]).startswith("ms:"):
+        return _worker_ms(d, outp)
     X, up, goal, obs = d["X"], d["up"], d["goal"], d["obs"]
     params = d["params"].item() if "params" in d.files else None
     B = X.shape[0]
@@ -155,7 +259,7 @@ def mpc_cbf_solve_many(X, up, goal, obs, params=None, workers=None, timeout=900)
 
 def _run(extra, X, up, goal, obs, params, workers, timeout):
     B = X.shape[0]
-    workers = max(1, min(workers or (os.cpu_count() or 2), 64, B))
+    workers = max(1, min(workers or MAX_WORKERS, MAX_WORKERS, os.cpu_count() or 2, B))
     edges = np.linspace(0, B, workers + 1).astype(int)
     with tempfile.TemporaryDirectory() as tmp:
         procs = []

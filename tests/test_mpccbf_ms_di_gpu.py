@@ -3,9 +3,6 @@
 which rescales the velocity to norm v_max) under IPOPT's algorithm -- against oracle/ms_ipopt.py with di_model() in the kernel's profile:
 same status and same iteration count problem by problem, |u0 - u0_oracle| <= 1e-8, on draws with and without a feasible point and with the
 velocity rescaling active inside the rows."""
-import os
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -16,6 +13,7 @@ import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import workloads as W  # noqa: E402
 from safe_control_amd.robots.spec import complete_robot_spec  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import ms_batch, ms_solve_many, take  # noqa: E402
 
 DEV = "cuda:0"
 SPEC = {"model": "DoubleIntegrator2D"}
@@ -31,37 +29,31 @@ def di_oracle_model():
     return MS.di_model({k: v for k, v in sp.items() if k in keys})
 
 
-def _one(args):
-    x, up, g, ob, N = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    u, st, it, info = MS.solve(di_oracle_model(), x, up, g, ob, N=N, return_info=True, opts=dict(MS.KERNEL_PROFILE))
-    return u, st, it, np.concatenate([info["X"].reshape(-1), info["U"].reshape(-1)])
-
-
 def oracle_many(X, up, goal, obs, N=None):
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        return p.map(_one, [(X[i], up[i], goal[i], obs[i], N) for i in range(len(X))], chunksize=2)
+    """oracle/ms_ipopt.py (kernel 13's profile) on every row, in the host's child-process pool (tests/_oracle_pool.py)."""
+    return ms_solve_many("di", X, up, goal, obs, opts=dict(MS.KERNEL13_PROFILE), N=N, spec=SPEC)
 
 
 def compare(u, st, it, plan, res, n_off):
-    so, ito = np.array([r[1] for r in res]), np.array([r[2] for r in res])
+    so, ito = res["st"], res["it"]
     assert np.array_equal(st, so), np.flatnonzero(st != so)[:10]
     off = it != ito
     assert off.sum() <= n_off and np.abs(it - ito).max() <= 2, (int(off.sum()), int(np.abs(it - ito).max()))
-    du = np.array([np.abs(u[i] - r[0]).max() for i, r in enumerate(res)])
+    du = np.abs(u - res["u"]).max(axis=1)
     assert du[~off].max() <= 1e-8 and du.max() <= 1e-6, (du[~off].max(), du.max())
     if plan is not None:
-        dp = np.array([np.abs(plan[i] - r[3]).max() for i, r in enumerate(res)])
+        dp = np.abs(plan - res["plan"]).max(axis=1)
         assert dp[(so == 0) & ~off].max() <= 1e-6, dp[(so == 0) & ~off].max()
     return so, ito
 
 
 def test_bench_draws_against_the_oracle():
     n = 384
-    X, up, goal, obs = (a[:n] for a in W.mpc_family_batch("di", 4096, 8, seed=0))
+    (X, up, goal, obs), res = ms_batch("di", 0, opts=dict(MS.KERNEL13_PROFILE), spec=SPEC)      # (the session's run over all 4096: tests/test_mpccbf_ms_full_batch_gpu.py)
+    X, up, goal, obs, res = X[:n], up[:n], goal[:n], obs[:n], take(res, slice(0, n))
     ctl = sca.BatchedMSMPCCBF(SPEC, io_dtype="f64")
     u, st, it, plan = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs), want_plan=True))
-    so, ito = compare(u, st, it, plan, oracle_many(X, up, goal, obs), n_off=6)
+    so, ito = compare(u, st, it, plan, res, n_off=6)
     assert 0.02 <= (so == 1).mean() <= 0.2 and (so == 2).mean() <= 0.01
     print(f"di ms kernel: optimal {np.mean(so == 0):.4f}, infeasible {np.mean(so == 1):.4f}, iterations mean {ito.mean():.1f} max {ito.max()}")
 

@@ -4,9 +4,6 @@ which clips the speed to [v_min, v_max]) under IPOPT's algorithm -- against orac
 inputs enter the positions directly (general stage layout: two columns of A and all of B per stage).  Where the plan slows down to v_min the
 clip's kink sits on the solution and Newton's method cycles around it (IPOPT would, too: casadi differentiates fmin / fmax piecewise): those
 solves run to the iteration limit on both sides, along paths that rounding separates after ~50 iterations -- they are compared by status only."""
-import os
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -17,6 +14,7 @@ import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import workloads as W  # noqa: E402
 from safe_control_amd.robots.spec import complete_robot_spec  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import ms_batch  # noqa: E402
 
 DEV = "cuda:0"
 SPEC = {"model": "KinematicBicycle2D"}
@@ -32,20 +30,13 @@ def kb_oracle_model():
     return MS.kb_model({k: v for k, v in sp.items() if k in MS.kb_model()["spec"]})
 
 
-def _one(args):
-    x, up, g, ob = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    return MS.solve(kb_oracle_model(), x, up, g, ob, opts=dict(MS.KERNEL_PROFILE, max_iter=LIMIT))
-
-
 def test_bench_draws_against_the_oracle():
     n = 320
-    X, up, goal, obs = (a[:n] for a in W.mpc_family_batch("kb", 4096, 8, seed=0))
+    (X, up, goal, obs), res = ms_batch("kb", 0, opts=dict(MS.KERNEL13_PROFILE, max_iter=LIMIT), spec=SPEC)      # (the session's run over all 4096)
+    X, up, goal, obs = X[:n], up[:n], goal[:n], obs[:n]
     ctl = sca.BatchedMSMPCCBF(SPEC, io_dtype="f64", max_iter=LIMIT)
     u, st, it = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs)))
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        res = p.map(_one, [(X[i], up[i], goal[i], obs[i]) for i in range(n)], chunksize=2)
-    uo, so, ito = np.array([r[0] for r in res]), np.array([r[1] for r in res]), np.array([r[2] for r in res])
+    uo, so, ito = res["u"][:n], res["st"][:n], res["it"][:n]
     assert (st == so).mean() >= 0.99, np.flatnonzero(st != so)[:10]
     short = ito < 60                                                        # (the solves that end before rounding can separate two paths)
     assert short.mean() >= 0.9 and np.array_equal(st[short], so[short])

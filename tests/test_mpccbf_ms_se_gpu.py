@@ -3,9 +3,6 @@ whose DT barriers have that branch -- dynamic_unicycle2D.py:204-220, double_inte
 in the obstacle's frame) against oracle/ms_ipopt.py (StageNLP._h serves the branch; pinned to the reference's registered constraint values on
 superellipsoid draws by tests/test_oracle_ms.py): mixed scenes of circles and superellipsoids, same status, same iteration count,
 |u0 - u0_oracle| <= 1e-8; the host-side class picks the instantiation from the rows' flags."""
-import os
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -14,8 +11,8 @@ pytestmark = pytest.mark.gpu
 
 import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import workloads as W  # noqa: E402
-from safe_control_amd.robots.spec import complete_robot_spec  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import mixed_scene, ms_cached, take  # noqa: E402
 
 DEV = "cuda:0"
 SPECS = {"du": {"model": "DynamicUnicycle2D", "a_max": 1.0, "w_max": 0.5, "v_max": 1.0, "radius": 0.25}, "di": {"model": "DoubleIntegrator2D"}}
@@ -25,35 +22,15 @@ def t(a, dtype=torch.float64):
     return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=DEV)
 
 
-def model_of(fam):
-    sp = complete_robot_spec(dict(SPECS[fam]))
-    mk = {"du": MS.du_model, "di": MS.di_model}[fam]
-    return mk({k: v for k, v in sp.items() if k in mk()["spec"]})
-
-
-def _one(args):
-    fam, x, up, g, ob = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    return MS.solve(model_of(fam), x, up, g, ob, opts=dict(MS.KERNEL_PROFILE))
-
-
-def mixed_scene(fam, n, seed=3):
-    X, up, goal, obs = (a[:n].copy() for a in W.mpc_family_batch(fam, 4096, 8, seed=0))
-    se = W.superellipsoid_obstacles(X[:, :2], 8, seed=seed, radius=0.25, rho_max=2.5)
-    mix = np.random.default_rng(1).random((n, 8)) < 0.6
-    obs[mix] = se[mix]
-    return X, up, goal, obs
-
-
 @pytest.mark.parametrize("fam", ["du", "di"])
 def test_mixed_scenes_against_the_oracle(fam):
     n = 160
-    X, up, goal, obs = mixed_scene(fam, n)
+    X, up, goal, obs = mixed_scene(fam, 1024)                                  # (the first 160 of the 1024 scenes tests/test_mpccbf_ms_full_batch_gpu.py
+    res = ms_cached(fam, ("mixed_scene", 1024), X, up, goal, obs, opts=dict(MS.KERNEL13_PROFILE), spec=SPECS[fam])     # holds to the oracle: one run)
+    X, up, goal, obs, res = X[:n], up[:n], goal[:n], obs[:n], take(res, slice(0, n))
     ctl = sca.BatchedMSMPCCBF(dict(SPECS[fam]), io_dtype="f64")
     u, st, it = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs)))
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        res = p.map(_one, [(fam, X[i], up[i], goal[i], obs[i]) for i in range(n)], chunksize=2)
-    uo, so, ito = np.array([r[0] for r in res]), np.array([r[1] for r in res]), np.array([r[2] for r in res])
+    uo, so, ito = res["u"], res["st"], res["it"]
     # (a solve of more than 128 tiny steps fills the kernel's filter and ends 'inaccurate' where IPOPT's unbounded filter goes on: one in 128 here)
     short = ito <= 120
     assert short.mean() >= 0.97 and np.array_equal(st[short], so[short])

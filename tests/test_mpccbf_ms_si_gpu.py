@@ -2,9 +2,6 @@
 (position_control/mpc_cbf.py:19-21,49-51,135-141,183-187,312-315; robots/single_integrator2D.py:45-66,148-190: two states, inputs (vx, vy), one-step
 rows) under IPOPT's algorithm -- against oracle/ms_ipopt.py with si_model() in the kernel's profile: same status, same iteration count,
 |u0 - u0_oracle| <= 1e-8.  The kernel holds the robot as four states, two of them idle; circles only."""
-import os
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -14,6 +11,7 @@ pytestmark = pytest.mark.gpu
 import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import workloads as W  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import ms_batch, ms_solve_many, take  # noqa: E402
 
 DEV = "cuda:0"
 SPEC = {"model": "SingleIntegrator2D"}
@@ -23,34 +21,29 @@ def t(a, dtype=torch.float64):
     return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=DEV)
 
 
-def _one(args):
-    x, up, g, ob = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    return MS.solve(MS.si_model(), x, up, g, ob, opts=dict(MS.KERNEL_PROFILE))
-
-
 def oracle_many(X, up, goal, obs):
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        return p.map(_one, [(X[i], up[i], goal[i], obs[i]) for i in range(len(X))], chunksize=2)
+    """oracle/ms_ipopt.py (kernel 13's profile) on every row, in the host's child-process pool (tests/_oracle_pool.py)."""
+    return ms_solve_many("si", X, up, goal, obs, opts=dict(MS.KERNEL13_PROFILE), spec=SPEC)
 
 
 def compare(u, st, it, res, n_off):
-    so, ito = np.array([r[1] for r in res]), np.array([r[2] for r in res])
+    so, ito = res["st"], res["it"]
     assert np.array_equal(st, so), np.flatnonzero(st != so)[:10]
     off = it != ito
     assert off.sum() <= n_off and np.abs(it - ito).max() <= 2, (int(off.sum()), int(np.abs(it - ito).max()))
-    du = np.array([np.abs(u[i] - r[0]).max() for i, r in enumerate(res)])
+    du = np.abs(u - res["u"]).max(axis=1)
     assert du[~off].max() <= 1e-8 and du.max() <= 1e-6, (du[~off].max(), du.max())
     return so, ito
 
 
 def test_bench_draws_and_a_crowded_scene_against_the_oracle():
     n = 256
-    X, up, goal, obs = (a[:n].copy() for a in W.mpc_family_batch("si", 4096, 8, seed=0))
+    (X, up, goal, obs), res = ms_batch("si", 0, opts=dict(MS.KERNEL13_PROFILE), spec=SPEC)      # (the session's run over all 4096: tests/test_mpccbf_ms_full_batch_gpu.py)
+    X, up, goal, obs, res = X[:n].copy(), up[:n].copy(), goal[:n].copy(), obs[:n].copy(), take(res, slice(0, n))
     assert X.shape[1] == 2 and not (obs[..., 6] >= 0.5).any()
     ctl = sca.BatchedMSMPCCBF(SPEC, io_dtype="f64")
     u, st, it = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs)))           # two-column state rows, as the reference's
-    so, ito = compare(u, st, it, oracle_many(X, up, goal, obs), n_off=4)
+    so, ito = compare(u, st, it, res, n_off=4)
     rng = np.random.default_rng(7)
     m = 128
     ob2 = obs[:m].copy()

@@ -2,9 +2,6 @@
 (position_control/mpc_cbf.py:22-24,52-53,135-141,188-192,312-315; robots/unicycle2D.py:42-68,127-146: three states, inputs (v, omega), ONE-step
 rows d_h + alpha h_k >= 0) under IPOPT's algorithm -- against oracle/ms_ipopt.py with uni_model() in the kernel's profile: same status, same
 iteration count, |u0 - u0_oracle| <= 1e-8.  The kernel holds the robot as four states, the last one idle."""
-import os
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -15,6 +12,7 @@ import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import workloads as W  # noqa: E402
 from safe_control_amd.robots.spec import complete_robot_spec  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import ms_batch, ms_solve_many, take  # noqa: E402
 
 DEV = "cuda:0"
 SPEC = {"model": "Unicycle2D"}
@@ -29,39 +27,32 @@ def uni_oracle_model():
     return MS.uni_model({k: v for k, v in sp.items() if k in MS.uni_model()["spec"]})
 
 
-def _one(args):
-    x, up, g, ob, N = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    u, st, it, info = MS.solve(uni_oracle_model(), x, up, g, ob, N=N, return_info=True, opts=dict(MS.KERNEL_PROFILE))
-    return u, st, it, np.concatenate([info["X"].reshape(-1), info["U"].reshape(-1)])
-
-
 def oracle_many(X, up, goal, obs, N=None):
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        return p.map(_one, [(X[i], up[i], goal[i], obs[i], N) for i in range(len(X))], chunksize=2)
+    """oracle/ms_ipopt.py (kernel 13's profile) on every row, in the host's child-process pool (tests/_oracle_pool.py)."""
+    return ms_solve_many("uni", X, up, goal, obs, opts=dict(MS.KERNEL13_PROFILE), N=N, spec=SPEC)
 
 
 def compare(u, st, it, res, n_off):
-    so, ito = np.array([r[1] for r in res]), np.array([r[2] for r in res])
+    so, ito = res["st"], res["it"]
     assert np.array_equal(st, so), np.flatnonzero(st != so)[:10]
     off = it != ito
     assert off.sum() <= n_off and np.abs(it - ito).max() <= 2, (int(off.sum()), int(np.abs(it - ito).max()))
-    du = np.array([np.abs(u[i] - r[0]).max() for i, r in enumerate(res)])
+    du = np.abs(u - res["u"]).max(axis=1)
     assert du[~off].max() <= 1e-8 and du.max() <= 1e-6, (du[~off].max(), du.max())
     return so, ito
 
 
 def test_bench_draws_and_a_crowded_scene_against_the_oracle():
     n = 256
-    X, up, goal, obs = (a[:n].copy() for a in W.mpc_family_batch("uni", 4096, 8, seed=0))
+    (X, up, goal, obs), res = ms_batch("uni", 0, opts=dict(MS.KERNEL13_PROFILE), spec=SPEC)     # (the session's run over all 4096: tests/test_mpccbf_ms_full_batch_gpu.py)
+    X, up, goal, obs, res = X[:n].copy(), up[:n].copy(), goal[:n].copy(), obs[:n].copy(), take(res, slice(0, n))
     ctl = sca.BatchedMSMPCCBF(SPEC, io_dtype="f64")
     u, st, it, plan = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs), want_plan=True))
-    res = oracle_many(X, up, goal, obs)
     so, ito = compare(u, st, it, res, n_off=4)
     # the plan: states as four columns (the idle one stays zero), the oracle's as three
     P4 = plan[:, : 11 * 4].reshape(n, 11, 4)
     assert np.abs(P4[:, :, 3]).max() == 0.0
-    Po = np.array([r[3][: 11 * 3].reshape(11, 3) for r in res])
+    Po = res["plan"][:, : 11 * 3].reshape(n, 11, 3)
     assert np.abs(P4[:, :, :3] - Po)[so == 0].max() <= 1e-6
     # obstacles pulled to within 0.6 m of the robot and a last input at full speed: rows active or violated at the start
     rng = np.random.default_rng(7)

@@ -4,10 +4,6 @@ elastic variables on the CBF rows, stall rule): SAME STATUS and SAME ITERATION C
 tolerance), |u0 - u0_oracle| <= 1e-8 (1e-7 on those), plans (positions of ~100 m, weakly determined far down the horizon) to 1e-5; the traces of the two solvers (E_0, infeasibilities, mu, theta, delta_w, alpha per
 iteration) agree to 1e-5 relative over the first 15 iterations.  Then the restoration phase inside the kernel against the oracle's, the hand-over to
 the condensed kernel when no workspace is given, f32 storage, shared obstacles, 16 row slots, the optimal-decay instantiation."""
-import os
-import sys
-from multiprocessing import Pool
-
 import numpy as np
 import pytest
 
@@ -17,6 +13,7 @@ pytestmark = pytest.mark.gpu
 import safe_control_amd as sca  # noqa: E402
 from safe_control_amd import _lib, workloads as W  # noqa: E402
 from oracle import ms_ipopt as MS  # noqa: E402
+from _oracle_pool import ms_solve_many  # noqa: E402
 
 DEV = "cuda:0"
 PROFILE = dict(MS.KERNEL_PROFILE)                  # what the kernel runs: Riccati linear algebra, no second-order corrections, restoration on the CBF rows, stall rule
@@ -26,18 +23,14 @@ def t(a, dtype=torch.float64):
     return torch.tensor(np.ascontiguousarray(a), dtype=dtype, device=DEV)
 
 
-def _one(args):
-    x, up, g, ob, spec = args[:5]
-    os.environ["OMP_NUM_THREADS"] = "1"
-    tr = []
-    u, st, it, info = MS.solve(MS.vtol_model(spec), x, up, g, ob, return_info=True, opts=args[5] if len(args) > 5 else PROFILE, trace=tr)
-    T = np.array([[q["E0"], q["dinf"], q["pinf"], q["comp"], q["mu"], q["theta"], q["delta"], q["alpha"]] for q in tr])
-    return u, st, it, T, np.concatenate([info["X"].reshape(-1), info["U"].reshape(-1)])
-
-
 def oracle_many(X, up, goal, obs, spec=None, opts=None):
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        return p.map(_one, [(X[i], up[i], goal[i], obs[i] if obs.ndim == 3 else obs, spec, opts or PROFILE) for i in range(len(X))], chunksize=1)
+    """oracle/ms_ipopt.py on every row in the host's child-process pool (tests/_oracle_pool.py): per row (u, status, iterations, the first
+    iterates' trace [E0, dinf, pinf, comp, mu, theta, delta_w, alpha], plan)."""
+    r = ms_solve_many("vtol", X, up, goal, obs, opts=opts or PROFILE, spec=spec)
+    T = [r["trace"][i, :min(int(r["ntr"][i]), len(r["trace"][i]))].copy() for i in range(len(X))]
+    for q in T:
+        q[:, 7] = np.abs(q[:, 7])                                         # (this trace's step lengths are unsigned in the restoration, as the kernel's)
+    return [(r["u"][i], r["st"][i], r["it"][i], T[i], r["plan"][i]) for i in range(len(X))]
 
 
 def compare(u, st, it, plan, res, n_off=8):
@@ -173,11 +166,11 @@ def test_argument_validation():
     assert lib.sc_mpcvtol_ms_solve_batch(C.byref(p), C.byref(ip), 1, 8, *([None] * 10)) != _lib.SC_OK
 
 
-def _one_od(args):
-    x, up, g, ob = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    u, st, it, info = MS.solve(MS.vtol_od_model(), x, up, g, ob, return_info=True, opts=PROFILE)
-    return u[:4], st, it, info["U"][:, 4:].reshape(-1), info["f"]
+def oracle_od_many(X, up, goal, obs, N=30):
+    """The optimal-decay oracle on every row: per row (u_0, status, iterations, decay rates of the plan, f, restoration iterates)."""
+    r = ms_solve_many("vtol_od", X, up, goal, obs, opts=PROFILE)
+    U = r["plan"][:, (N + 1) * 6:].reshape(len(X), N, -1)                 # (the plan: X [N+1, 6], then U [N, 4 + 2])
+    return [(r["u"][i][:4], r["st"][i], r["it"][i], U[i, :, 4:].reshape(-1), r["f"][i], r["resto_iters"][i] + r["resto"][i]) for i in range(len(X))]
 
 
 def test_optimal_decay_instantiation_against_the_oracle():
@@ -196,8 +189,7 @@ def test_optimal_decay_instantiation_against_the_oracle():
     X, up, goal, obs = Xn[:n], up0[:n], gn[:n], on[:n]
     ctl = sca.BatchedOptimalDecayVtolMSMPCCBF(io_dtype="f64", fallback=False)
     u, rho, st, it = (a.cpu().numpy() for a in ctl.solve(t(X), t(up), t(goal), t(obs)))
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        res = p.map(_one_od, [(X[i], up[i], goal[i], obs[i]) for i in range(n)], chunksize=2)
+    res = oracle_od_many(X, up, goal, obs)
     so = np.array([q[1] for q in res]); ito = np.array([q[2] for q in res])
     assert (st == so).all(), np.flatnonzero(st != so)
     both = (st == 0) & (so == 0)
@@ -222,14 +214,6 @@ def test_optimal_decay_instantiation_against_the_oracle():
     assert torch.equal(u2[keep], u1[keep])
 
 
-def _one_od_resto(args):
-    x, up, g, ob = args
-    os.environ["OMP_NUM_THREADS"] = "1"
-    tr = []
-    u, st, it, info = MS.solve(MS.vtol_od_model(), x, up, g, ob, return_info=True, opts=PROFILE, trace=tr)
-    return u[:4], st, it, sum(1 for q in tr if q["resto"])
-
-
 def test_optimal_decay_solves_that_pass_through_the_restoration_phase():
     """The optimal-decay bench batch holds 33 problems (of 4096) on which the regular phase gives up (SC_STATUS_NEEDS_RESTO without a workspace):
     with the restoration phase inside the kernel they are solved there, and the oracle (KERNEL_PROFILE) walks the same way -- measured: 32 of
@@ -248,8 +232,7 @@ def test_optimal_decay_solves_that_pass_through_the_restoration_phase():
     assert 20 <= len(idx) <= 60
     ctl = sca.BatchedOptimalDecayVtolMSMPCCBF(io_dtype="f64", fallback=False)
     u, rho, st, it, tr = (a.cpu().numpy() for a in ctl.solve(t(Xn[idx]), t(up0[idx]), t(gn[idx]), t(on[idx]), want_trace=True))
-    with Pool(min(32, os.cpu_count() or 4)) as p:
-        res = p.map(_one_od_resto, [(Xn[i], up0[i], gn[i], on[i]) for i in idx], chunksize=1)
+    res = oracle_od_many(Xn[idx], up0[idx], gn[idx], on[idx])
     so = np.array([q[1] for q in res])
     du = np.array([np.abs(u[k] - q[0]).max() for k, q in enumerate(res)])
     nr = np.array([(tr[k, :it[k] + 1, 7] < 0).sum() for k in range(len(idx))])

@@ -338,3 +338,55 @@ def test_kernel_profile_returns_the_full_algorithms_input_on_config3_draws():
     du = np.array([np.abs(r[0][0] - r[1][0]).max() for r in res])
     assert (sa == sb).all() and (sb == 1).sum() >= 8
     assert du.max() <= 1e-8
+
+
+DU_SPEC = dict(a_max=1.0, w_max=0.5, v_max=1.0, radius=0.25)
+
+
+def test_info_names_the_rule_that_ended_the_solve():
+    """info["exit"] on configs[2] draws: a converged solve (tol), a certified infeasible one (the restoration's certificate), one cut by
+    max_iter, one ended by the stall rule (every step shorter than 1 counts as tiny here), each with its status code."""
+    from safe_control_amd import workloads as W
+    X, up, goal, obs = W.mpc_family_batch("du", 4096, 8, seed=0)
+    mdl = MS.du_model(DU_SPEC)
+    run = lambda i, **kw: MS.solve(mdl, X[i], up[i], goal[i], obs[i], return_info=True, opts=dict(MS.KERNEL13_PROFILE, **kw))   # noqa: E731
+    _, st, it, info = run(0)
+    assert (st, info["exit"], info["n_resto"]) == (0, "tol", 0) and 0 < info["filter_peak"] < 128
+    _, st, it, info = run(5)
+    assert (st, info["exit"]) == (1, "infeasible") and info["n_resto"] >= 1 and 0 < info["resto_iters"] < it
+    _, st, it, info = run(0, max_iter=5)
+    assert (st, it, info["exit"]) == (2, 5, "max_iter")
+    _, st, it, info = run(0, stall_iter=2, stall_alpha=1.0 + 1e-12)
+    assert (st, it, info["exit"]) == (2, 2, "stall")
+    assert set(MS.EXITS) >= {"tol", "acceptable", "infeasible", "max_iter", "stall", "floor", "filter_full", "resto_failed", "error"}
+    assert MS.KERNEL_PROFILE.get("filter_cap", 0) == 0                   # (kernel 12's profile: unbounded; KERNEL13_PROFILE adds the cap)
+
+
+def test_kernel13_profile_stops_where_the_filter_runs_over():
+    """Superellipsoid scene 131 of the 1024 mixed DynamicUnicycle2D scenes fills a 128-entry filter: KERNEL13_PROFILE ends it there with
+    status 2 (kernel 13's rule, after the step whose entry ran over), the unbounded filter goes on to converge; scenes whose filter stays
+    below 128 entries get identical results from the two profiles."""
+    from _oracle_pool import mixed_scene
+    X, up, goal, obs = mixed_scene("du", 1024)
+    mdl = MS.du_model(DU_SPEC)
+    u13, s13, i13, a = MS.solve(mdl, X[131], up[131], goal[131], obs[131], return_info=True, opts=dict(MS.KERNEL13_PROFILE))
+    u12, s12, i12, b = MS.solve(mdl, X[131], up[131], goal[131], obs[131], return_info=True, opts=dict(MS.KERNEL_PROFILE))
+    assert (s13, i13, a["exit"], a["filter_peak"]) == (2, 129, "filter_full", 128)
+    assert b["exit"] != "filter_full" and b["filter_peak"] > 128 and i12 > i13
+    assert (s12, b["exit"]) == (0, "tol")
+    for i in (0, 492, 721):                                               # (peaks of 10 - 122 entries)
+        ua, sa, ia, p = MS.solve(mdl, X[i], up[i], goal[i], obs[i], return_info=True, opts=dict(MS.KERNEL13_PROFILE))
+        ub, sb, ib, q = MS.solve(mdl, X[i], up[i], goal[i], obs[i], return_info=True, opts=dict(MS.KERNEL_PROFILE))
+        assert p["filter_peak"] == q["filter_peak"] < 128 and (sa, ia) == (sb, ib) and np.array_equal(ua, ub), i
+
+
+def test_gpu_tests_start_no_forked_pools():
+    """A forked child of a process that holds a HIP context inherits its device files and its runtime's threads: the GPU tests run their
+    oracles in tests/_oracle_pool.py's child processes, at most MAX_WORKERS at a time."""
+    import glob
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    hits = [p for p in sorted(glob.glob(os.path.join(here, "*_gpu.py"))) if re.search(r"\bmultiprocessing\b", open(p).read())]
+    assert hits == [], hits
+    from _oracle_pool import MAX_WORKERS
+    assert MAX_WORKERS <= 16
