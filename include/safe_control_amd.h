@@ -851,6 +851,62 @@ int sc_backupcbf_rollout_batch(const sc_backupcbf_params* params, int64_t B, int
                                void* X, void* bullet_x, void* u_out, int32_t* status_out, int32_t* using_backup_out,
                                void* h_min_out, int32_t* ret, int32_t* ret_step, void* stream);
 
+/* ---- Gatekeeper / MPS shielding on the evade scenario ----------------------------------------------------------------
+ * Gatekeeper.solve_control_problem (shielding/gatekeeper.py:553-672) and MPS.solve_control_problem (shielding/mps.py:59-166)
+ * in external-trajectory mode, on the composition examples/evade/test_evade.py --algo gatekeeper / mps builds (:335-385):
+ * DoubleIntegrator2D, EvadeBackupController, EvadeEnv's wall / pocket and bullet tests, the bullet predicted at constant speed.
+ * Per agent and call: the event test (current_time_idx >= next_event_time / dt), the candidate search (Gatekeeper: switching
+ * steps s = max(M - i d, 0) for i < M / d + 2, first valid wins; MPS: s = 1 only), commit / reschedule, the committed input at
+ * the index (or the backup input at the real state past its end), the index increment and is_using_backup().  The persistent
+ * state lives in a caller-owned device buffer of sc_shield_state_bytes() bytes, zeroed before the first call (= a fresh
+ * shield).  Layout (structure of arrays, C = max_nominal): committed nominal inputs double [B, C, 2]; backup cursor double
+ * [B, 4]; next_event_time double [B]; then int32 [B] each: committed nominal steps s, current_time_idx, committed length
+ * (= len(committed_u_traj) = s + n_backup), initialised.  The backup part of the commitment is not stored: the cursor starts at
+ * the switching state and steps once per index in it, the same operations as the reference's stored rollout.
+ */
+#define SC_SHIELD_GATEKEEPER 0
+#define SC_SHIELD_MPS        1
+#define SC_SHIELD_MAX_NOMINAL 512
+
+typedef struct sc_shield_params {
+    int32_t algo;                /* SC_SHIELD_GATEKEEPER / SC_SHIELD_MPS                                                 */
+    int32_t n_nominal;           /* M = len(nominal_x_traj) - 1 of this call; with NULL nominal inputs the device rolls out
+                                    the example's nominal controller for M steps (int(nominal_horizon / dt), test_evade.py:387) */
+    int32_t max_nominal;         /* C >= n_nominal, <= SC_SHIELD_MAX_NOMINAL: row stride of the state buffer and of the
+                                    committed trajectory outputs (keep it fixed for one state buffer)                     */
+    int32_t n_backup;            /* int(backup_horizon / dt) (gatekeeper.py:327), >= 0                                   */
+    int32_t discount_steps;      /* max(1, int(horizon_discount / dt)) (gatekeeper.py:595), >= 1; MPS ignores it          */
+    int32_t predict_bullet;      /* 1: the moving-obstacle test against get_obstacles(t) (set_moving_obstacles), 0: none */
+    double  event_offset;        /* gatekeeper.py:539,663                                                                 */
+    sc_backupcbf_params base;    /* io_dtype, bullet_shared, dt, robot_radius, a_max, v_max, safety_margin (the shield's),
+                                    backup_kp / backup_kd, EvadeEnv geometry; n_steps, backup_horizon, fd_eps, alpha,
+                                    alpha_terminal are not read                                                          */
+} sc_shield_params;
+
+/* Bytes of the persistent state of B agents (0 when params is NULL or invalid, or B < 0). */
+size_t sc_shield_state_bytes(const sc_shield_params* params, int64_t B);
+
+/* One control step.  X [B,4] (robot_state); bullet_x [B] or [1] (EvadeEnv.bullet_x: the current bullet of
+ * check_obstacle_collision, and the base of the prediction); nominal_x [B, M+1, 4] and nominal_u [B, M, 2]
+ * (set_nominal_trajectory) or both NULL for the example's nominal controller rolled out on the device from X; state as above
+ * (in / out); u_out [B,2]; using_backup_out [B] (is_using_backup() after the call) and nominal_steps_out [B]
+ * (actual_nominal_steps) may be NULL; committed_x [B, C+1+n_backup, 4] / committed_u [B, C+n_backup, 2] may be NULL, else
+ * the committed trajectory (get_committed_trajectory(), first committed length + 1 / committed length rows) is written
+ * there whenever it changes (first call, commit).  io_dtype is the element type of X, bullet_x, the nominal inputs, u_out
+ * and the committed trajectory. */
+int sc_shield_step_batch(const sc_shield_params* params, int64_t B, const void* X, const void* bullet_x,
+                         const void* nominal_x, const void* nominal_u, void* state, void* u_out, int32_t* using_backup_out,
+                         int32_t* nominal_steps_out, void* committed_x, void* committed_u, void* stream);
+
+/* The example's closed loop (test_evade.py:434-497), n_ctrl control steps in one launch: nominal rollout on the device ->
+ * shield -> robot.step -> speed clamp -> step_bullet (respawn past the hallway) -> collision / goal checks.  X [B,4] and
+ * bullet_x [B] (bullet_shared must be 0) in / out; ret / ret_step as sc_backupcbf_rollout_batch; backup_steps [B] in / out
+ * (may be NULL): += is_using_backup() per executed step (the example's backup_ratio numerator); u_out / using_backup_out:
+ * values of the last step. */
+int sc_shield_rollout_batch(const sc_shield_params* params, int64_t B, int32_t n_ctrl, int32_t step_offset, void* X,
+                            void* bullet_x, void* state, void* u_out, int32_t* using_backup_out, int32_t* ret,
+                            int32_t* ret_step, int32_t* backup_steps, void* stream);
+
 /* ---- control_step around the solve for Quad2D / Quad3D (SURVEY 8f-1 over the 8f-3 models) ----------------------------------
  * The split of sc_tracking_select_batch / sc_tracking_apply_batch for the two quadrotor models, whose states (6 / 12), inputs
  * (2 / 4) and goals (2-D / 3-D) do not fit the 4-state kernels: LocalTrackingController.control_step (tracking.py:559-668) with

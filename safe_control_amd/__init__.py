@@ -19,6 +19,7 @@ from .position_control.backup_cbf_qp import BackupCBF, BatchedBackupCBF  # noqa:
 from .position_control.optimal_decay_cbf_qp import OptimalDecayCBFQP, BatchedOptimalDecayCBFQP  # noqa: F401
 from .position_control.optimal_decay_mpc_cbf import OptimalDecayMPCCBF, BatchedOptimalDecayMPCCBF  # noqa: F401
 from .position_control.optimal_decay_mpc_cbf_gn import OptimalDecayGnMPCCBF, BatchedOptimalDecayGnMPCCBF  # noqa: F401
+from .shielding import MPS, BatchedShield, Gatekeeper  # noqa: F401
 from .robots.spec import RobotHandle, complete_robot_spec  # noqa: F401
 from .tracking import BatchedTrackingController, BatchedFleetTrackingController  # noqa: F401
 

@@ -72,6 +72,18 @@ class BackupCbfParams(C.Structure):
     ]
 
 
+SHIELD_GATEKEEPER, SHIELD_MPS = 0, 1
+SHIELD_MAX_NOMINAL = 512
+
+
+class ShieldParams(C.Structure):
+    """Mirror of ``sc_shield_params``."""
+    _fields_ = [
+        ("algo", C.c_int32), ("n_nominal", C.c_int32), ("max_nominal", C.c_int32), ("n_backup", C.c_int32),
+        ("discount_steps", C.c_int32), ("predict_bullet", C.c_int32), ("event_offset", C.c_double), ("base", BackupCbfParams),
+    ]
+
+
 MPCCBF_MAX_HORIZON = 32
 
 
@@ -364,6 +376,9 @@ SYMBOLS = {
     "sc_quadtrack_apply_batch": (C.c_int, [C.POINTER(QuadTrackParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
     "sc_backupcbf_solve_batch": (C.c_int, [C.POINTER(BackupCbfParams), C.c_int64] + [C.c_void_p] * 10),
     "sc_backupcbf_rollout_batch": (C.c_int, [C.POINTER(BackupCbfParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+    "sc_shield_state_bytes": (C.c_size_t, [C.POINTER(ShieldParams), C.c_int64]),
+    "sc_shield_step_batch": (C.c_int, [C.POINTER(ShieldParams), C.c_int64] + [C.c_void_p] * 11),
+    "sc_shield_rollout_batch": (C.c_int, [C.POINTER(ShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
     "sc_tracking_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10),

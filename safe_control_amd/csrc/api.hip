@@ -53,6 +53,10 @@ hipError_t quadtrack_apply_launch(const sc_quadtrack_params& p, long long B, int
 hipError_t backupcbf_launch(const sc_backupcbf_params& p, long long B, int n_ctrl, int advance, void* X, const void* u_nom,
                             void* bullet_x, void* u_out, int* status, int* using_backup, void* h_min, int* n_rows, double* rows_out,
                             int* ret, int* ret_step, int step0, hipStream_t stream);
+size_t shield_state_bytes(long long B, int C);
+hipError_t shield_launch(const sc_shield_params& p, long long B, int n_ctrl, int advance, void* X, void* bullet_x, const void* nom_x,
+                         const void* nom_u, void* state, void* u_out, int* using_out, int* s_out, void* cx_out, void* cu_out, int* ret,
+                         int* ret_step, int* backup_steps, int step0, hipStream_t stream);
 
 size_t mpclin_lds_bytes(int N, int K, int nx, int nu, bool od = false);
 size_t mpclin_model_doubles(int nx, int nu, int N);
@@ -654,6 +658,67 @@ int sc_backupcbf_rollout_batch(const sc_backupcbf_params* params, int64_t B, int
     hipError_t e = sc::backupcbf_launch(*params, (long long)B, n_ctrl, 1, X, nullptr, bullet_x, u_out, status_out, using_backup_out,
                                         h_min_out, nullptr, nullptr, ret, ret_step, step_offset, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "backup-CBF rollout kernel launch");
+    return SC_OK;
+}
+
+static int check_shield(const sc_shield_params* p, int64_t B) {
+    if (!p) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (B < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0");
+    if (p->algo != SC_SHIELD_GATEKEEPER && p->algo != SC_SHIELD_MPS)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "algo must be SC_SHIELD_GATEKEEPER or SC_SHIELD_MPS");
+    const sc_backupcbf_params& b = p->base;
+    if (b.io_dtype != SC_DTYPE_F32 && b.io_dtype != SC_DTYPE_F64)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "base.io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (p->max_nominal > SC_SHIELD_MAX_NOMINAL) return sc::fail(SC_ERR_UNSUPPORTED, "max_nominal > SC_SHIELD_MAX_NOMINAL");
+    if (p->n_nominal < 0 || p->max_nominal < 1 || p->n_nominal > p->max_nominal)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "need 0 <= n_nominal <= max_nominal and max_nominal >= 1");
+    if (p->n_backup < 0 || p->n_backup > (1 << 20)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_backup outside [0, 2^20]");
+    if (p->discount_steps < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "discount_steps < 1 (max(1, int(horizon_discount / dt)))");
+    if (p->predict_bullet != 0 && p->predict_bullet != 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "predict_bullet must be 0 or 1");
+    if (b.bullet_shared != 0 && b.bullet_shared != 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "base.bullet_shared must be 0 or 1");
+    if (!(p->event_offset >= 0) || !(p->event_offset < 1e300)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "event_offset must be finite and >= 0");
+    if (!(b.dt > 0) || !(b.a_max > 0) || !(b.v_max > 0) || !(b.robot_radius >= 0) || !(b.safety_margin >= 0))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt, a_max, v_max must be > 0, robot_radius and safety_margin >= 0");
+    if (!(b.pocket_x_min < b.pocket_x_max) || !(b.pocket_y_min < b.pocket_y_max) || !(b.half_width > 0) || !(b.hallway_length > 0) ||
+        !(b.bullet_length > 0) || !(b.bullet_width > 0))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "degenerate EvadeEnv geometry");
+    return SC_OK;
+}
+
+size_t sc_shield_state_bytes(const sc_shield_params* params, int64_t B) {
+    if (check_shield(params, B) != SC_OK) return 0;
+    return sc::shield_state_bytes((long long)B, params->max_nominal);
+}
+
+int sc_shield_step_batch(const sc_shield_params* params, int64_t B, const void* X, const void* bullet_x, const void* nominal_x,
+                         const void* nominal_u, void* state, void* u_out, int32_t* using_backup_out, int32_t* nominal_steps_out,
+                         void* committed_x, void* committed_u, void* stream) {
+    int rc = check_shield(params, B);
+    if (rc != SC_OK) return rc;
+    if (B > 0 && (!X || !bullet_x || !state || !u_out)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if ((nominal_x == nullptr) != (nominal_u == nullptr)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "pass nominal_x and nominal_u, or neither");
+    if (B == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::shield_launch(*params, (long long)B, 1, 0, const_cast<void*>(X), const_cast<void*>(bullet_x), nominal_x, nominal_u,
+                                     state, u_out, using_backup_out, nominal_steps_out, committed_x, committed_u, nullptr, nullptr, nullptr,
+                                     0, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "shield kernel launch");
+    return SC_OK;
+}
+
+int sc_shield_rollout_batch(const sc_shield_params* params, int64_t B, int32_t n_ctrl, int32_t step_offset, void* X, void* bullet_x,
+                            void* state, void* u_out, int32_t* using_backup_out, int32_t* ret, int32_t* ret_step, int32_t* backup_steps,
+                            void* stream) {
+    int rc = check_shield(params, B);
+    if (rc != SC_OK) return rc;
+    if (n_ctrl < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_ctrl < 0");
+    if (params->base.bullet_shared) return sc::fail(SC_ERR_INVALID_ARGUMENT, "the closed loop needs one bullet per agent (bullet_shared = 0)");
+    if (B > 0 && (!X || !bullet_x || !state || !u_out || !ret || !ret_step)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B == 0 || n_ctrl == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::shield_launch(*params, (long long)B, n_ctrl, 1, X, bullet_x, nullptr, nullptr, state, u_out, using_backup_out, nullptr,
+                                     nullptr, nullptr, ret, ret_step, backup_steps, step_offset, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "shield rollout kernel launch");
     return SC_OK;
 }
 
