@@ -907,6 +907,84 @@ int sc_shield_rollout_batch(const sc_shield_params* params, int64_t B, int32_t n
                             void* bullet_x, void* state, void* u_out, int32_t* using_backup_out, int32_t* ret,
                             int32_t* ret_step, int32_t* backup_steps, void* stream);
 
+/* ---- Gatekeeper / MPS shielding on the drift-car scenario ---------------------------------------------------------------
+ * The same two shields (see the sc_shield_* block) on the composition examples/drift_car/test_drift.py --algo gatekeeper / mps
+ * --backup lane_change / stop builds (:209-373): the 8-state DriftingCar (x, y, theta, r, beta, V, delta, tau; inputs delta_dot,
+ * tau_dot) on DynamicBicycle2D.step with the Fiala tyre (robots/dynamic_bicycle2D.py:103-388, robots/drifting_car.py:474-530),
+ * LaneChangeController or StoppingController as the backup (position_control/backup_controller.py:126-195, 305-354), and the
+ * three collision tests of Gatekeeper._is_collision on a straight DriftingEnv: the track boundary through the nearest of the
+ * 100 centre-line samples (envs/drifting_env.py:340-371), static obstacle circles with the plain robot radius, and moving
+ * obstacle rectangles at time k dt with radius + safety margin.  Every rollout of a call uses that call's friction.
+ * Persistent state in a caller-owned device buffer of sc_drift_shield_state_bytes() bytes, zeroed = fresh shields.  Layout
+ * (structure of arrays, C = max_nominal): committed nominal inputs double [B, C, 2]; backup cursor double [B, 8]; friction of
+ * the commitment double [B] (the stored backup inputs of the reference were computed with the friction at commit time; the
+ * cursor replays them with it); next_event_time double [B]; then int32 [B] each: committed nominal steps s,
+ * current_time_idx, committed length (s + n_backup), initialised.
+ * Obstacle tables: static [n_static, 3] = x, y, radius; moving [n_moving, 7] = x, y, vx, vy, length, width, radius (the radius
+ * is read by the closed loop's circle test only); one table per car ([B, n, .]) or, with obs_shared, one for all ([n, .]).
+ */
+#define SC_DRIFT_LANE_CHANGE 0
+#define SC_DRIFT_STOP        1
+#define SC_DRIFT_TRACK_STRAIGHT 0          /* 'oval' / 'l_shape' (1, 2) are refused with SC_ERR_UNSUPPORTED */
+#define SC_DRIFT_MAX_OBS     8
+#define SC_DRIFT_MAX_PUDDLES 4
+#define SC_DRIFT_CENTER_SAMPLES 100
+#define SC_DRIFT_MAX_NOMINAL 256            /* two cars' nominal trajectories share one workgroup's LDS */
+
+typedef struct sc_drift_controller {       /* gains and limits read off the controller object                                  */
+    int32_t kind;                /* SC_DRIFT_LANE_CHANGE / SC_DRIFT_STOP                                                       */
+    int32_t reserved;
+    double  target_y;            /* lane change: the target lane centre                                                        */
+    double  kp_y, kd_y, kp_theta, kd_theta, kp_delta, kp_v, kp_tau_dot, v_target, theta_des_max;
+    double  delta_max, delta_dot_max, tau_max, tau_dot_max;
+    double  stop_velocity, min_braking_torque, holding_torque;                  /* stop only                                   */
+} sc_drift_controller;
+
+typedef struct sc_drift_shield_params {
+    int32_t algo;                /* SC_SHIELD_GATEKEEPER / SC_SHIELD_MPS                                                       */
+    int32_t io_dtype;            /* element type of every float array except the state buffer                                 */
+    int32_t track_type;          /* SC_DRIFT_TRACK_STRAIGHT                                                                    */
+    int32_t n_nominal;           /* M of this call (with NULL nominal inputs: steps of the device-side lane keeper)           */
+    int32_t max_nominal;         /* C >= n_nominal, <= SC_DRIFT_MAX_NOMINAL                                                    */
+    int32_t n_backup;            /* int(backup_horizon / dt)                                                                   */
+    int32_t discount_steps;      /* max(1, int(horizon_discount / dt))                                                         */
+    int32_t n_static, n_moving;  /* rows of the obstacle tables, each <= SC_DRIFT_MAX_OBS                                      */
+    int32_t obs_shared;          /* 1: one static and one moving table for all cars (step only)                               */
+    int32_t n_puddles;           /* rows of `puddles` in use (closed loop only), <= SC_DRIFT_MAX_PUDDLES                       */
+    int32_t reserved;
+    double  dt, event_offset, safety_margin, robot_radius;
+    double  a, b, m, Iz, Cc_f, Cc_r, r_w, gamma;                                 /* DynamicBicycle2D                           */
+    double  delta_max, tau_max, r_max, beta_max, v_min, v_max;                   /* the five state clamps                      */
+    double  track_length, track_width;
+    double  mu_default;          /* robot_spec['mu'] of the example: friction outside every puddle (closed loop)              */
+    double  puddles[SC_DRIFT_MAX_PUDDLES][4];                                    /* x, y, radius, friction                     */
+    sc_drift_controller backup;  /* the backup controller                                                                      */
+    sc_drift_controller keeper;  /* the lane keeper that plans the nominal trajectory on the device (kind LANE_CHANGE)         */
+} sc_drift_shield_params;
+
+/* Bytes of the persistent state of B cars (0 when params is NULL or invalid, or B < 0). */
+size_t sc_drift_shield_state_bytes(const sc_drift_shield_params* params, int64_t B);
+
+/* One solve_control_problem(state, friction) per car.  X [B,8]; friction [B]; static_obs / moving_obs as above (NULL when the
+ * count is 0); nominal_x [B, M+1, 8] and nominal_u [B, M, 2] (set_nominal_trajectory) or both NULL for the lane keeper rolled
+ * out on the device from X; state in / out; u_out [B,2]; using_backup_out [B] (Gatekeeper: current_time_idx >= s; MPS:
+ * |u - nominal_u[0]| >= 1e-2, mps.py:146-158) and nominal_steps_out [B] may be NULL; committed_x [B, C+1+n_backup, 8] /
+ * committed_u [B, C+n_backup, 2] may be NULL, else written whenever the commitment changes. */
+int sc_drift_shield_step_batch(const sc_drift_shield_params* params, int64_t B, const void* X, const void* friction,
+                               const void* static_obs, const void* moving_obs, const void* nominal_x, const void* nominal_u,
+                               void* state, void* u_out, int32_t* using_backup_out, int32_t* nominal_steps_out,
+                               void* committed_x, void* committed_u, void* stream);
+
+/* The example's loop (test_drift.py:433-510), n_ctrl steps in one launch: friction from the puddle table at the car's position
+ * with the 0.01 hysteresis -> lane keeper rollout -> shield -> car.step -> step_dynamic_obstacles -> check_collision
+ * (drifting_car.py:676-711: |y| against half_width - radius, circles for both obstacle kinds) -> end of track (x before the
+ * step > track_length - 10).  X [B,8], friction [B], moving_obs [B, n_moving, 7] (obs_shared must be 0) in / out; ret [B]:
+ * 0 running, 1 end of track, -2 collision; ret_step [B] the step it happened at (step_offset + local step); backup_steps [B]
+ * in / out (may be NULL): += is_using_backup(); u_out / using_backup_out: values of the last executed step. */
+int sc_drift_shield_rollout_batch(const sc_drift_shield_params* params, int64_t B, int32_t n_ctrl, int32_t step_offset, void* X,
+                                  void* friction, const void* static_obs, void* moving_obs, void* state, void* u_out,
+                                  int32_t* using_backup_out, int32_t* ret, int32_t* ret_step, int32_t* backup_steps, void* stream);
+
 /* ---- control_step around the solve for Quad2D / Quad3D (SURVEY 8f-1 over the 8f-3 models) ----------------------------------
  * The split of sc_tracking_select_batch / sc_tracking_apply_batch for the two quadrotor models, whose states (6 / 12), inputs
  * (2 / 4) and goals (2-D / 3-D) do not fit the 4-state kernels: LocalTrackingController.control_step (tracking.py:559-668) with

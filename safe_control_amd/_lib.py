@@ -84,6 +84,31 @@ class ShieldParams(C.Structure):
     ]
 
 
+DRIFT_LANE_CHANGE, DRIFT_STOP = 0, 1
+DRIFT_TRACK_STRAIGHT = 0
+DRIFT_MAX_OBS, DRIFT_MAX_PUDDLES, DRIFT_MAX_NOMINAL = 8, 4, 256
+
+DRIFT_CTRL_KEYS = ("target_y", "kp_y", "kd_y", "kp_theta", "kd_theta", "kp_delta", "kp_v", "kp_tau_dot", "v_target", "theta_des_max",
+                   "delta_max", "delta_dot_max", "tau_max", "tau_dot_max", "stop_velocity", "min_braking_torque", "holding_torque")
+
+
+class DriftController(C.Structure):
+    """Mirror of ``sc_drift_controller``."""
+    _fields_ = [("kind", C.c_int32), ("reserved", C.c_int32)] + [(k, C.c_double) for k in DRIFT_CTRL_KEYS]
+
+
+DRIFT_VEHICLE_KEYS = ("a", "b", "m", "Iz", "Cc_f", "Cc_r", "r_w", "gamma", "delta_max", "tau_max", "r_max", "beta_max", "v_min", "v_max")
+
+
+class DriftShieldParams(C.Structure):
+    """Mirror of ``sc_drift_shield_params``."""
+    _fields_ = [(k, C.c_int32) for k in ("algo", "io_dtype", "track_type", "n_nominal", "max_nominal", "n_backup", "discount_steps",
+                                         "n_static", "n_moving", "obs_shared", "n_puddles", "reserved")] + \
+               [(k, C.c_double) for k in ("dt", "event_offset", "safety_margin", "robot_radius") + DRIFT_VEHICLE_KEYS +
+                ("track_length", "track_width", "mu_default")] + \
+               [("puddles", (C.c_double * 4) * DRIFT_MAX_PUDDLES), ("backup", DriftController), ("keeper", DriftController)]
+
+
 MPCCBF_MAX_HORIZON = 32
 
 
@@ -379,6 +404,9 @@ SYMBOLS = {
     "sc_shield_state_bytes": (C.c_size_t, [C.POINTER(ShieldParams), C.c_int64]),
     "sc_shield_step_batch": (C.c_int, [C.POINTER(ShieldParams), C.c_int64] + [C.c_void_p] * 11),
     "sc_shield_rollout_batch": (C.c_int, [C.POINTER(ShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 9),
+    "sc_drift_shield_state_bytes": (C.c_size_t, [C.POINTER(DriftShieldParams), C.c_int64]),
+    "sc_drift_shield_step_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64] + [C.c_void_p] * 13),
+    "sc_drift_shield_rollout_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "sc_tracking_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10),

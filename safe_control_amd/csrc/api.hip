@@ -54,6 +54,10 @@ hipError_t backupcbf_launch(const sc_backupcbf_params& p, long long B, int n_ctr
                             void* bullet_x, void* u_out, int* status, int* using_backup, void* h_min, int* n_rows, double* rows_out,
                             int* ret, int* ret_step, int step0, hipStream_t stream);
 size_t shield_state_bytes(long long B, int C);
+size_t drift_shield_state_bytes(long long B, int C);
+hipError_t drift_shield_launch(const sc_drift_shield_params& p, long long B, int n_ctrl, int advance, void* X, void* friction, const void* sob,
+                               void* mob, const void* nom_x, const void* nom_u, void* state, void* u_out, int* using_out, int* s_out,
+                               void* cx_out, void* cu_out, int* ret, int* ret_step, int* backup_steps, int step0, hipStream_t stream);
 hipError_t shield_launch(const sc_shield_params& p, long long B, int n_ctrl, int advance, void* X, void* bullet_x, const void* nom_x,
                          const void* nom_u, void* state, void* u_out, int* using_out, int* s_out, void* cx_out, void* cu_out, int* ret,
                          int* ret_step, int* backup_steps, int step0, hipStream_t stream);
@@ -719,6 +723,88 @@ int sc_shield_rollout_batch(const sc_shield_params* params, int64_t B, int32_t n
     hipError_t e = sc::shield_launch(*params, (long long)B, n_ctrl, 1, X, bullet_x, nullptr, nullptr, state, u_out, using_backup_out, nullptr,
                                      nullptr, nullptr, ret, ret_step, backup_steps, step_offset, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "shield rollout kernel launch");
+    return SC_OK;
+}
+
+static int check_drift_ctrl(const sc_drift_controller& c, const char* who) {
+    if (c.kind != SC_DRIFT_LANE_CHANGE && c.kind != SC_DRIFT_STOP) return sc::fail(SC_ERR_UNSUPPORTED, who);
+    if (!(c.delta_max > 0) || !(c.delta_dot_max > 0) || !(c.tau_max > 0) || !(c.tau_dot_max > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, who);
+    if (c.kind == SC_DRIFT_LANE_CHANGE && !(c.theta_des_max > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, who);
+    return SC_OK;
+}
+
+static int check_drift_shield(const sc_drift_shield_params* p, int64_t B) {
+    if (!p) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (B < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0");
+    if (p->algo != SC_SHIELD_GATEKEEPER && p->algo != SC_SHIELD_MPS)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "algo must be SC_SHIELD_GATEKEEPER or SC_SHIELD_MPS");
+    if (p->io_dtype != SC_DTYPE_F32 && p->io_dtype != SC_DTYPE_F64) return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (p->track_type != SC_DRIFT_TRACK_STRAIGHT) return sc::fail(SC_ERR_UNSUPPORTED, "only the straight track is served (track_type 'oval' / 'l_shape' are not)");
+    if (p->max_nominal > SC_DRIFT_MAX_NOMINAL) return sc::fail(SC_ERR_UNSUPPORTED, "max_nominal > SC_DRIFT_MAX_NOMINAL");
+    if (p->n_nominal < 0 || p->max_nominal < 1 || p->n_nominal > p->max_nominal)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "need 0 <= n_nominal <= max_nominal and max_nominal >= 1");
+    if (p->n_backup < 0 || p->n_backup > (1 << 20)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_backup outside [0, 2^20]");
+    if (p->discount_steps < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "discount_steps < 1 (max(1, int(horizon_discount / dt)))");
+    if (p->n_static < 0 || p->n_moving < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "negative obstacle count");
+    if (p->n_static > SC_DRIFT_MAX_OBS || p->n_moving > SC_DRIFT_MAX_OBS) return sc::fail(SC_ERR_UNSUPPORTED, "more than SC_DRIFT_MAX_OBS obstacles of a kind");
+    if (p->n_puddles < 0 || p->n_puddles > SC_DRIFT_MAX_PUDDLES) return sc::fail(SC_ERR_UNSUPPORTED, "n_puddles outside [0, SC_DRIFT_MAX_PUDDLES]");
+    if (p->obs_shared != 0 && p->obs_shared != 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "obs_shared must be 0 or 1");
+    if (!(p->event_offset >= 0) || !(p->event_offset < 1e300)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "event_offset must be finite and >= 0");
+    if (!(p->dt > 0) || !(p->robot_radius >= 0) || !(p->safety_margin >= 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0, robot_radius and safety_margin >= 0");
+    if (!(p->a > 0) || !(p->b > 0) || !(p->m > 0) || !(p->Iz > 0) || !(p->Cc_f > 0) || !(p->Cc_r > 0) || !(p->r_w > 0) || !(p->gamma >= 0))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "a, b, m, Iz, Cc_f, Cc_r, r_w must be > 0 and gamma >= 0");
+    if (!(p->delta_max > 0) || !(p->tau_max > 0) || !(p->r_max > 0) || !(p->beta_max > 0) || !(p->v_min <= p->v_max))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "delta_max, tau_max, r_max, beta_max must be > 0 and v_min <= v_max");
+    if (!(p->track_length > 0) || !(p->track_width > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "degenerate track");
+    int rc = check_drift_ctrl(p->backup, "backup controller: kind must be SC_DRIFT_LANE_CHANGE or SC_DRIFT_STOP with positive limits");
+    if (rc != SC_OK) return rc;
+    return SC_OK;
+}
+
+size_t sc_drift_shield_state_bytes(const sc_drift_shield_params* params, int64_t B) {
+    if (check_drift_shield(params, B) != SC_OK) return 0;
+    return sc::drift_shield_state_bytes((long long)B, params->max_nominal);
+}
+
+int sc_drift_shield_step_batch(const sc_drift_shield_params* params, int64_t B, const void* X, const void* friction, const void* static_obs,
+                               const void* moving_obs, const void* nominal_x, const void* nominal_u, void* state, void* u_out,
+                               int32_t* using_backup_out, int32_t* nominal_steps_out, void* committed_x, void* committed_u, void* stream) {
+    int rc = check_drift_shield(params, B);
+    if (rc != SC_OK) return rc;
+    if (B > 0 && (!X || !friction || !state || !u_out)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B > 0 && ((params->n_static > 0 && !static_obs) || (params->n_moving > 0 && !moving_obs)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL obstacle table with a positive count");
+    if ((nominal_x == nullptr) != (nominal_u == nullptr)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "pass nominal_x and nominal_u, or neither");
+    if (!nominal_x) {
+        rc = check_drift_ctrl(params->keeper, "lane keeper: kind must be SC_DRIFT_LANE_CHANGE with positive limits");
+        if (rc != SC_OK) return rc;
+    }
+    if (B == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::drift_shield_launch(*params, (long long)B, 1, 0, const_cast<void*>(X), const_cast<void*>(friction), static_obs,
+                                           const_cast<void*>(moving_obs), nominal_x, nominal_u, state, u_out, using_backup_out, nominal_steps_out,
+                                           committed_x, committed_u, nullptr, nullptr, nullptr, 0, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "drift shield kernel launch");
+    return SC_OK;
+}
+
+int sc_drift_shield_rollout_batch(const sc_drift_shield_params* params, int64_t B, int32_t n_ctrl, int32_t step_offset, void* X, void* friction,
+                                  const void* static_obs, void* moving_obs, void* state, void* u_out, int32_t* using_backup_out, int32_t* ret,
+                                  int32_t* ret_step, int32_t* backup_steps, void* stream) {
+    int rc = check_drift_shield(params, B);
+    if (rc != SC_OK) return rc;
+    if (n_ctrl < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_ctrl < 0");
+    if (params->obs_shared) return sc::fail(SC_ERR_INVALID_ARGUMENT, "the closed loop moves the obstacles: it needs one table per car (obs_shared = 0)");
+    rc = check_drift_ctrl(params->keeper, "lane keeper: kind must be SC_DRIFT_LANE_CHANGE with positive limits");
+    if (rc != SC_OK) return rc;
+    if (B > 0 && (!X || !friction || !state || !u_out || !ret || !ret_step)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B > 0 && ((params->n_static > 0 && !static_obs) || (params->n_moving > 0 && !moving_obs)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL obstacle table with a positive count");
+    if (B == 0 || n_ctrl == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::drift_shield_launch(*params, (long long)B, n_ctrl, 1, X, friction, static_obs, moving_obs, nullptr, nullptr, state, u_out,
+                                           using_backup_out, nullptr, nullptr, nullptr, ret, ret_step, backup_steps, step_offset, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "drift shield rollout kernel launch");
     return SC_OK;
 }
 
