@@ -47,17 +47,43 @@ static inline bool sc_force_lds_kernel() {
 using as1_void = const __attribute__((address_space(1))) void;
 using as3_void = __attribute__((address_space(3))) void;
 
-// State row -> (x0..x4) in the compute type.  4-state models: two 8/16-byte loads; Quad2D: six values per row.
-template <typename TIO, typename TC, int MODEL>
-__device__ __forceinline__ Agent<TC> load_agent(const TIO* __restrict__ X, long long agent) {
+// State row -> (x0..x4) in the compute type.  4-state models: two 8/16-byte loads; Quad2D: six values per row, five of them used.
+// The loads (load_state) and the conversion with its sincos (to_agent) are separate so that a kernel can issue every input load
+// before it waits for any of them.
+template <typename TIO, int MODEL>
+struct StateRow { TIO v[MODEL == SC_MODEL_QUAD2D ? 5 : 4]; };
+
+template <typename TIO, int MODEL>
+__device__ __forceinline__ StateRow<TIO, MODEL> load_state(const TIO* __restrict__ X, long long agent) {
+    StateRow<TIO, MODEL> s;
     if constexpr (MODEL == SC_MODEL_QUAD2D) {
         const TIO* r = X + agent * 6;
-        return make_agent_m<TC, MODEL>(TC(r[0]), TC(r[1]), TC(r[2]), TC(r[3]), TC(r[4]));
+#pragma unroll
+        for (int i = 0; i < 5; ++i) s.v[i] = r[i];
     } else {
         const TIO* r = X + agent * 4;
-        return make_agent_m<TC, MODEL>(TC(r[0]), TC(r[1]), TC(r[2]), TC(r[3]));
+#pragma unroll
+        for (int i = 0; i < 4; ++i) s.v[i] = r[i];
     }
+    return s;
 }
+
+template <typename TIO, typename TC, int MODEL>
+__device__ __forceinline__ Agent<TC> to_agent(const StateRow<TIO, MODEL>& s) {
+    if constexpr (MODEL == SC_MODEL_QUAD2D) return make_agent_m<TC, MODEL>(TC(s.v[0]), TC(s.v[1]), TC(s.v[2]), TC(s.v[3]), TC(s.v[4]));
+    else return make_agent_m<TC, MODEL>(TC(s.v[0]), TC(s.v[1]), TC(s.v[2]), TC(s.v[3]));
+}
+
+template <typename TIO, typename TC, int MODEL>
+__device__ __forceinline__ Agent<TC> load_agent(const TIO* __restrict__ X, long long agent) {
+    return to_agent<TIO, TC, MODEL>(load_state<TIO, MODEL>(X, agent));
+}
+
+// By-value kernel arguments past the preloaded ones are read with scalar loads, which the compiler sinks to each argument's first
+// use: one cold round trip to the argument block after another, each behind the input loads' wait.  Naming a value here makes its
+// load issue at this point instead, i.e. while the input loads are in flight.
+template <typename T>
+__device__ __forceinline__ void fetch_arg_now(const T& v) { asm volatile("" ::"s"(v)); }
 
 template <typename TIO> struct vec2;
 template <> struct vec2<float> { using type = float2; };
@@ -95,11 +121,11 @@ template <> struct vec4io<double> { using type = double2; static constexpr int N
 //   2  the generic body for exactly the waves pass 1 deferred (it reads status_out first; the others leave at once).
 #define SC_STATUS_PENDING (-1)
 template <typename TIO, typename TC, int KMAX, int MODEL, int PASS = 0>
-__global__ __launch_bounds__(256) void cbfqp_reg_kernel(const sc_cbfqp_params p, const long long B, const int K,
-                                                        const TIO* __restrict__ X, const TIO* __restrict__ u_ref,
-                                                        const TIO* __restrict__ obs, const int* __restrict__ n_obs,
+__global__ __launch_bounds__(256) void cbfqp_reg_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
+                                                        const TIO* __restrict__ u_ref, const int* __restrict__ n_obs,
+                                                        const long long B, const int K, const int obs_shared,
                                                         TIO* __restrict__ u_out, int* __restrict__ status_out,
-                                                        TIO* __restrict__ h_out) {
+                                                        TIO* __restrict__ h_out, const CbfConsts<TC> k) {
     const long long agent = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     const bool active = agent < B;
     const long long ag_i = active ? agent : 0;           // inactive lanes compute on agent 0, store nothing
@@ -113,7 +139,7 @@ __global__ __launch_bounds__(256) void cbfqp_reg_kernel(const sc_cbfqp_params p,
 
     // ---- loads: obstacles first (longest latency), then state ---------------------------
     TIO flat[KMAX * 7];
-    const TIO* src = obs + (p.obs_shared ? 0 : (size_t)ag_i * K * 7);
+    const TIO* src = obs + (obs_shared ? 0 : (size_t)ag_i * K * 7);
     if (K == KMAX && ((KMAX * 7) % VN == 0) && ((reinterpret_cast<uintptr_t>(obs) & 15u) == 0) &&
         ((KMAX * 7 * sizeof(TIO)) % 16 == 0)) {
         const V4* s4 = reinterpret_cast<const V4*>(src);
@@ -134,11 +160,10 @@ __global__ __launch_bounds__(256) void cbfqp_reg_kernel(const sc_cbfqp_params p,
         }
     }
     const V2 ur = reinterpret_cast<const V2*>(u_ref)[ag_i];
+    const StateRow<TIO, MODEL> xs = load_state<TIO, MODEL>(X, ag_i);
     int nk = K;
-    if (n_obs) {
-        nk = n_obs[ag_i];
-        nk = nk < 0 ? 0 : (nk > K ? K : nk);
-    }
+    if (n_obs) nk = n_obs[ag_i];                           // issued with the other loads; clamped once they are all in flight
+    nk = nk < 0 ? 0 : (nk > K ? K : nk);
     if constexpr (PASS == 1) {
         bool other = false;
 #pragma unroll
@@ -149,8 +174,7 @@ __global__ __launch_bounds__(256) void cbfqp_reg_kernel(const sc_cbfqp_params p,
         }
     }
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
-    const CbfConsts<TC> k = make_consts<TC>(p);
-    const Agent<TC> ag = load_agent<TIO, TC, MODEL>(X, ag_i);
+    const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
 
     // ---- rows: agent_barrier + cbf_qp.py:155-183, unrolled, in registers ------------------
     TC n0[KMAX], n1[KMAX], c[KMAX];
@@ -211,15 +235,23 @@ __global__ __launch_bounds__(256) void cbfqp_reg_kernel(const sc_cbfqp_params p,
 // the wave-uniform "nobody violates row i" skip fires most of the time.  Arithmetic per row is the
 // same code as the lane-per-QP kernel (min/max reductions are exact), so both give the same answer.
 // G lanes per agent (G = 8, 16 or 32 >= K), 64 / G agents per wave.
+// Parameters are in order of first use: the first 14 dwords (obs .. u_out) arrive in SGPRs at wave start (kernel-argument
+// preloading, FLAGS_cbf_qp_* in the Makefile), so the input loads go out without a scalar-load round trip in front of them; the
+// rest is fetched while those loads are in flight.  The other two kernels of this file keep the same order.
 template <typename TIO, typename TC, int G, int MODEL>
 #ifndef SC_COOP_WAVES
 #define SC_COOP_WAVES 1                                   // waves per workgroup of the cooperative kernel (developer builds time 2 and 4)
 #endif
-__global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const sc_cbfqp_params p, const long long B, const int K,
-                                                        const TIO* __restrict__ X, const TIO* __restrict__ u_ref,
-                                                        const TIO* __restrict__ obs, const int* __restrict__ n_obs,
+__global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
+                                                        const TIO* __restrict__ u_ref, const int* __restrict__ n_obs,
+                                                        const long long B, const int K, const int obs_shared,
                                                         TIO* __restrict__ u_out, int* __restrict__ status_out,
-                                                        TIO* __restrict__ h_out) {
+                                                        TIO* __restrict__ h_out, const CbfConsts<TC> k) {
+    // Developer builds only (tools/README.md): the attribution ladder of DESIGN.md 1b.  SC_EXP_EMPTY: the same grid with no body;
+    // SC_EXP_ARGS: the kernel arguments and one store that depends on them; SC_EXP_LOADS: the input loads and the product's stores.
+#ifdef SC_EXP_EMPTY
+    return;
+#endif
     constexpr int APW = 64 / G;                            // agents per wave
     const int lane = threadIdx.x & 63;
     const int sub = lane & (G - 1);                        // obstacle row handled by this lane
@@ -227,21 +259,39 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const sc
     const bool active = agent < B;
     const long long ag_i = active ? agent : 0;
     using V2 = typename vec2<TIO>::type;
+#ifdef SC_EXP_ARGS
+    if (active && sub == 0)
+        status_out[agent] = (int)((reinterpret_cast<uintptr_t>(obs) ^ reinterpret_cast<uintptr_t>(X) ^ reinterpret_cast<uintptr_t>(u_ref) ^
+                                   reinterpret_cast<uintptr_t>(n_obs) ^ reinterpret_cast<uintptr_t>(u_out) ^ reinterpret_cast<uintptr_t>(h_out)) >> 4) + K + obs_shared;
+    return;
+#endif
 
     TIO orow[7];
     const bool has_row = sub < K;
-    const TIO* src = obs + (p.obs_shared ? 0 : (size_t)ag_i * K * 7) + (has_row ? sub * 7 : 0);
+    const TIO* src = obs + (obs_shared ? 0 : (size_t)ag_i * K * 7) + (has_row ? sub * 7 : 0);
 #pragma unroll
     for (int f = 0; f < 7; ++f) orow[f] = src[f];
     const V2 ur = reinterpret_cast<const V2*>(u_ref)[ag_i];
+    const StateRow<TIO, MODEL> xs = load_state<TIO, MODEL>(X, ag_i);
     int nk = K;
-    if (n_obs) {
-        nk = n_obs[ag_i];
-        nk = nk < 0 ? 0 : (nk > K ? K : nk);
+    if (n_obs) nk = n_obs[ag_i];                           // issued with the other loads; clamped once they are all in flight
+    nk = nk < 0 ? 0 : (nk > K ? K : nk);
+    fetch_arg_now(status_out); fetch_arg_now(h_out);
+    fetch_arg_now(k.R); fetch_arg_now(k.g1); fetch_arg_now(k.g2);
+    fetch_arg_now(k.lo0); fetch_arg_now(k.hi0); fetch_arg_now(k.lo1); fetch_arg_now(k.hi1); fetch_arg_now(k.hard);
+#ifdef SC_EXP_LOADS
+    if (active) {
+        if (sub == 0) {
+            V2 uo; uo.x = ur.x + xs.v[0] + xs.v[1]; uo.y = ur.y + xs.v[2] + xs.v[3];
+            reinterpret_cast<V2*>(u_out)[agent] = uo;
+            status_out[agent] = nk;
+        }
+        if (h_out && has_row) h_out[agent * K + sub] = orow[0] + orow[1] + orow[2] + orow[3] + orow[4] + orow[5] + orow[6];
     }
+    return;
+#endif
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
-    const CbfConsts<TC> k = make_consts<TC>(p);
-    const Agent<TC> ag = load_agent<TIO, TC, MODEL>(X, ag_i);
+    const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
 
     // ---- this lane's row -------------------------------------------------------------------
     TC o[7];
@@ -256,6 +306,8 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const sc
     const bool used = sub < nk;
     const bool bad_mine = used && !ok;
     a0 = used ? a0 : TC(0); a1 = used ? a1 : TC(0); cc = used ? cc : TC(0);
+    // h(x) is final here: its store (two thirds of the launch's output bytes) leaves before the solve, not after it
+    if (active && h_out && has_row) h_out[agent * K + sub] = used ? TIO(h) : TIO(0);
     TC poison = TC(0);
     normalise_row(a0, a1, cc, poison);
 
@@ -289,7 +341,6 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const sc
             reinterpret_cast<V2*>(u_out)[agent] = uo;
             status_out[agent] = st;
         }
-        if (h_out && has_row) h_out[agent * K + sub] = used ? TIO(h) : TIO(0);
     }
 }
 
@@ -299,8 +350,10 @@ static hipError_t launch_coop(const sc_cbfqp_params& p, long long B, int K, cons
                               hipStream_t stream) {
     constexpr int APW = 64 / G;
     const unsigned nblk = (unsigned)((B + APW * SC_COOP_WAVES - 1) / (APW * SC_COOP_WAVES));
-    hipLaunchKernelGGL((cbfqp_coop_kernel<TIO, TC, G, MODEL>), dim3(nblk), dim3(64 * SC_COOP_WAVES), 0, stream, p, B, K,
-                       (const TIO*)X, (const TIO*)u_ref, (const TIO*)obs, n_obs, (TIO*)u_out, status, (TIO*)h_out);
+    const CbfConsts<TC> k = make_consts<TC>(p);           // once per launch, on the host: the kernel gets the finished constants
+    hipLaunchKernelGGL((cbfqp_coop_kernel<TIO, TC, G, MODEL>), dim3(nblk), dim3(64 * SC_COOP_WAVES), 0, stream,
+                       (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,
+                       (TIO*)u_out, status, (TIO*)h_out, k);
     return hipGetLastError();
 }
 
@@ -318,11 +371,11 @@ static hipError_t launch_coop(const sc_cbfqp_params& p, long long B, int K, cons
 // LDS bank (stride K*7 dwords) then read different rows, which removes the 8- (K = 8) to 16-way
 // (K = 16) bank conflict of the straightforward order; the QP does not care about row order.
 template <typename TIO, typename TC, int KMAX, int MODEL>
-__global__ __launch_bounds__(64) void cbfqp_kernel(const sc_cbfqp_params p, const long long B, const int K,
-                                                   const TIO* __restrict__ X, const TIO* __restrict__ u_ref,
-                                                   const TIO* __restrict__ obs, const int* __restrict__ n_obs,
+__global__ __launch_bounds__(64) void cbfqp_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
+                                                   const TIO* __restrict__ u_ref, const int* __restrict__ n_obs,
+                                                   const long long B, const int K, const int obs_shared,
                                                    TIO* __restrict__ u_out, int* __restrict__ status_out,
-                                                   TIO* __restrict__ h_out) {
+                                                   TIO* __restrict__ h_out, const CbfConsts<TC> k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     TIO* lobs = reinterpret_cast<TIO*>(smem);
 
@@ -334,7 +387,7 @@ __global__ __launch_bounds__(64) void cbfqp_kernel(const sc_cbfqp_params p, cons
     const int row_elems = K * 7;
 
     // ---- 1. obstacles: HBM -> LDS ------------------------------------------------
-    if (p.obs_shared) {
+    if (obs_shared) {
         for (int e = lane; e < row_elems; e += 64) lobs[e] = obs[e];
     } else {
         const TIO* src = obs + (size_t)first * row_elems;
@@ -349,31 +402,27 @@ __global__ __launch_bounds__(64) void cbfqp_kernel(const sc_cbfqp_params p, cons
 
     // state / reference (coalesced, overlaps the DMA)
     using V2 = typename vec2<TIO>::type;
-    TC ur0 = 0, ur1 = 0;
+    const long long ag_i = active ? agent : 0;            // inactive lanes read agent 0 (B >= 1), store nothing
+    const V2 ur = reinterpret_cast<const V2*>(u_ref)[ag_i];
+    const StateRow<TIO, MODEL> xs = load_state<TIO, MODEL>(X, ag_i);
     int nk = K;
-    if (active) {
-        const V2 ur = reinterpret_cast<const V2*>(u_ref)[agent];
-        ur0 = TC(ur.x); ur1 = TC(ur.y);
-        if (n_obs) {
-            nk = n_obs[agent];
-            nk = nk < 0 ? 0 : (nk > K ? K : nk);
-        }
-    }
-    const CbfConsts<TC> k = make_consts<TC>(p);
-    const Agent<TC> ag = load_agent<TIO, TC, MODEL>(X, active ? agent : 0);
+    if (n_obs) nk = n_obs[ag_i];                           // issued with the other loads; clamped once they are all in flight
+    nk = !active ? K : (nk < 0 ? 0 : (nk > K ? K : nk));
+    const TC ur0 = active ? TC(ur.x) : TC(0), ur1 = active ? TC(ur.y) : TC(0);
+    const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // LDS-DMA landed (it is tracked by vmcnt)
     __syncthreads();
 
     // ---- 2. row assembly: agent_barrier + cbf_qp.py:155-183 ------------------------
-    const size_t stage_bytes = ((p.obs_shared ? (size_t)row_elems : (size_t)64 * row_elems) * sizeof(TIO) + 15) & ~(size_t)15;
+    const size_t stage_bytes = ((obs_shared ? (size_t)row_elems : (size_t)64 * row_elems) * sizeof(TIO) + 15) & ~(size_t)15;
     TC* rows = reinterpret_cast<TC*>(smem + stage_bytes);          // [K][3][64]
     TIO* hl = reinterpret_cast<TIO*>(rows + (size_t)K * 3 * 64);   // [K][64], natural obstacle order
-    const TIO* mine = lobs + (p.obs_shared ? 0 : lane * row_elems);
+    const TIO* mine = lobs + (obs_shared ? 0 : lane * row_elems);
     int period = 32;                                               // P = 32 / gcd(K, 32)
     while (((K * (32 / period)) & 31) != 0 && period > 1) period >>= 1;
     // (period ends as the smallest power of two with K*32/period = 0 mod 32, i.e. 32/gcd(K,32))
-    const int rot = p.obs_shared ? 0 : (lane / period) % K;
+    const int rot = obs_shared ? 0 : (lane / period) % K;
     bool bad_obs = false;
     TC poison = TC(0);                                             // NaN once any row entry is non-finite
 #pragma nounroll
@@ -453,19 +502,23 @@ static hipError_t launch_one(const sc_cbfqp_params& p, long long B, int K, const
             return launch_coop<TIO, TC, 8, MODEL>(p, B, K, X, u_ref, obs, n_obs, u_out, status, h_out, stream);
         const unsigned threads = 256;
         const unsigned nblk = (unsigned)((B + threads - 1) / threads);
+        const CbfConsts<TC> k = make_consts<TC>(p);
         if constexpr (MODEL == SC_MODEL_DYNAMIC_UNICYCLE2D && sizeof(TC) == 8) {
             if (sc_two_pass() && B >= (1 << 18)) {            // below, the second launch costs more than the fast pass gains (2^16: 12.2 -> 13.4 us)
-                hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL, 1>), dim3(nblk), dim3(threads), 0, stream, p, B, K,
-                                   (const TIO*)X, (const TIO*)u_ref, (const TIO*)obs, n_obs, (TIO*)u_out, status, (TIO*)h_out);
+                hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL, 1>), dim3(nblk), dim3(threads), 0, stream,
+                                   (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,
+                                   (TIO*)u_out, status, (TIO*)h_out, k);
                 hipError_t e = hipGetLastError();
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL, 2>), dim3(nblk), dim3(threads), 0, stream, p, B, K,
-                                   (const TIO*)X, (const TIO*)u_ref, (const TIO*)obs, n_obs, (TIO*)u_out, status, (TIO*)h_out);
+                hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL, 2>), dim3(nblk), dim3(threads), 0, stream,
+                                   (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,
+                                   (TIO*)u_out, status, (TIO*)h_out, k);
                 return hipGetLastError();
             }
         }
-        hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL>), dim3(nblk), dim3(threads), 0, stream, p, B, K,
-                           (const TIO*)X, (const TIO*)u_ref, (const TIO*)obs, n_obs, (TIO*)u_out, status, (TIO*)h_out);
+        hipLaunchKernelGGL((cbfqp_reg_kernel<TIO, TC, KMAX, MODEL>), dim3(nblk), dim3(threads), 0, stream,
+                           (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,
+                           (TIO*)u_out, status, (TIO*)h_out, k);
         return hipGetLastError();
     } else {
     if (!sc_force_lds_kernel()) {                          // K > 8: one row per lane, 16 or 32 lanes per agent
@@ -473,6 +526,7 @@ static hipError_t launch_one(const sc_cbfqp_params& p, long long B, int K, const
         return launch_coop<TIO, TC, 32, MODEL>(p, B, K, X, u_ref, obs, n_obs, u_out, status, h_out, stream);
     }
     const unsigned blocks = (unsigned)((B + 63) / 64);
+    const CbfConsts<TC> k = make_consts<TC>(p);
     size_t lds = (p.obs_shared ? (size_t)K * 7 : (size_t)64 * K * 7) * sizeof(TIO);
     lds = ((lds + 15) & ~(size_t)15) + (size_t)K * 3 * 64 * sizeof(TC) + (KMAX > 0 ? (size_t)K * 64 * sizeof(TIO) : 0);
     auto kern = cbfqp_kernel<TIO, TC, KMAX, MODEL>;
@@ -485,8 +539,9 @@ static hipError_t launch_one(const sc_cbfqp_params& p, long long B, int K, const
             raised = true;
         }
     }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, K,
-                       (const TIO*)X, (const TIO*)u_ref, (const TIO*)obs, n_obs, (TIO*)u_out, status, (TIO*)h_out);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream,
+                       (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,
+                       (TIO*)u_out, status, (TIO*)h_out, k);
     return hipGetLastError();
     }
 }

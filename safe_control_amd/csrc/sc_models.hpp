@@ -9,7 +9,9 @@
 
 namespace sc {
 
-// Controller constants converted to the compute type once per kernel.
+// Controller constants in the compute type.  The CBF-QP kernels (cbf_qp_kernel.hpp) get them by value, filled on the host once per
+// launch; the closed-loop kernels still call make_consts themselves.  The build has no fast-math, so the double-precision
+// expressions below give the same bits on the host and on the device.
 template <typename T>
 struct CbfConsts {
     T R;           // robot radius
@@ -23,7 +25,7 @@ struct CbfConsts {
 };
 
 template <typename T>
-__device__ __forceinline__ CbfConsts<T> make_consts(const sc_cbfqp_params& p) {
+__host__ __device__ __forceinline__ CbfConsts<T> make_consts(const sc_cbfqp_params& p) {
     CbfConsts<T> k;
     k.R = T(p.robot_radius);
     k.a1 = T(p.alpha1);
