@@ -324,15 +324,17 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TI
 #endif
     qp_finish_box(S, k);
     TC worst = qp_row_margin(num<TC>::inf(), a0, a1, cc, S.u0, S.u1, poison);
-    worst = group_min<TC, G>(worst);
-    // NaN anywhere in the group must poison the status: min() drops NaN, so combine the flags explicitly
+    // NaN anywhere in the group must make the status infeasible, and min() drops NaN: a poisoned lane enters the minimum as -inf,
+    // which fails the slack check as the NaN did.  The group's bad-obstacle flags are its byte (G bits) of the wave's ballot.
     const bool nan_mine = !(poison == poison);
-    const unsigned long long nan_mask = __builtin_amdgcn_ballot_w64(nan_mine);
+    worst = nan_mine ? -num<TC>::inf() : worst;
+    if constexpr (G == 8) worst = min8_raw(worst);
+    else if constexpr (G == 16) worst = min16_raw(worst);
+    else worst = group_min<TC, G>(worst);
     const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
-    const unsigned long long grp = (G == 64 ? ~0ull : ((1ull << G) - 1ull)) << (lane & ~(G - 1));
-    if (nan_mask & grp) poison = num<TC>::nan();
-    int st = qp_status(S, worst, poison, k);
-    if (bad_mask & grp) st = SC_STATUS_BAD_OBSTACLE;
+    const bool bad_any = ((bad_mask >> (lane & ~(G - 1))) & (G == 64 ? ~0ull : ((1ull << G) - 1ull))) != 0ull;
+    int st = qp_status(S, worst, TC(0), k);
+    if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
     TC u0 = S.u0, u1 = S.u1;
     if (st != SC_STATUS_OPTIMAL) { u0 = num<TC>::nan(); u1 = num<TC>::nan(); }
     if (active) {

@@ -132,21 +132,93 @@ __device__ __forceinline__ T group_xor8(T v, T mirrored) {          // value of 
     else if constexpr (X == 6) return dpp_mov<0xB1>(mirrored);
     else return mirrored;
 }
-template <typename TC, int... Xs>
-__device__ __forceinline__ void clip_partners8(LineQP<TC>& L, TC a0, TC a1, TC cc, std::integer_sequence<int, Xs...>) {
-    const TC m0 = dpp_mov<0x141>(a0), m1 = dpp_mov<0x141>(a1), mc = dpp_mov<0x141>(cc);
-    (clip_row(L, group_xor8<TC, Xs + 1>(a0, m0), group_xor8<TC, Xs + 1>(a1, m1), group_xor8<TC, Xs + 1>(cc, mc)), ...);
+// ---- the shorter instruction stream of the two solves below -----------------------------------------------------------
+// A lone wave per SIMD issues one instruction every four to five cycles, whatever it is, so the solve's time is its executed
+// instruction count.  The helpers here compute the same values as fmin_ / fmax_ / clip_row / group_max with fewer
+// instructions; they are for the cooperative solves only (the other kernels keep the forms of sc_qp2.hpp).
+//
+// v_min / v_max without the canonicalising v_max(x, x) the compiler puts in front of an operand whose history it cannot see (a
+// value that came through a DPP move): that instruction only turns a signalling NaN into a quiet one, and no value here can be a
+// signalling NaN (inputs are converted from storage or produced by arithmetic, both of which quiet).  With IEEE mode on, a quiet
+// NaN operand yields the other operand, as fmin / fmax do.
+__device__ __forceinline__ float min_raw(float a, float b) { float r; asm("v_min_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float max_raw(float a, float b) { float r; asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double min_raw(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double max_raw(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float max_neg_raw(float a, float b) { float r; asm("v_max_f32 %0, %1, -%2" : "=v"(r) : "v"(a), "v"(b)); return r; }     // max(a, -b)
+__device__ __forceinline__ double max_neg_raw(double a, double b) { double r; asm("v_max_f64 %0, %1, -%2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ float max_abs_one_raw(float a) { float r; asm("v_max_f32 %0, |%1|, 1.0" : "=v"(r) : "v"(a)); return r; }            // max(|a|, 1)
+__device__ __forceinline__ double max_abs_one_raw(double a) { double r; asm("v_max_f64 %0, |%1|, 1.0" : "=v"(r) : "v"(a)); return r; }
+// keep ? v : a quiet NaN.  For a double only the high word is selected: the low word of a NaN is free, so it stays v's.
+__device__ __forceinline__ float keep_or_nan(bool keep, float v) { return keep ? v : __int_as_float(0x7fc00000); }
+__device__ __forceinline__ double keep_or_nan(bool keep, double v) {
+    return __hiloint2double(keep ? __double2hiint(v) : 0x7ff80000, __double2loint(v));
 }
-template <typename TC>
-__device__ __forceinline__ void coop_solve_all8(QpState<TC>& S, int K, int sub, int lane, TC a0, TC a1, TC cc,
-                                                const CbfConsts<TC>& k) {
+template <typename T>
+__device__ __forceinline__ T min8_raw(T v) {
+    v = min_raw(v, dpp_mov<0xB1>(v)); v = min_raw(v, dpp_mov<0x4E>(v)); v = min_raw(v, dpp_mov<0x141>(v));
+    return v;
+}
+template <typename T>
+__device__ __forceinline__ T min16_raw(T v) { v = min8_raw(v); return min_raw(v, dpp_mov<0x140>(v)); }
+// Bitwise OR over the group, for picking the value of ONE lane (every other lane passes 0): the DPP move folds into the 32-bit OR,
+// one instruction per word and step where a max of -inf-masked doubles takes four.
+template <int CTRL>
+__device__ __forceinline__ int or_dpp(int v) { return v | __builtin_amdgcn_update_dpp(0, v, CTRL, 0xf, 0xf, true); }
+template <int G>
+__device__ __forceinline__ int group_or_bits(int v) {
+    v = or_dpp<0xB1>(v); v = or_dpp<0x4E>(v); v = or_dpp<0x141>(v);
+    if constexpr (G == 16) v = or_dpp<0x140>(v);
+    return v;
+}
+template <int G>
+__device__ __forceinline__ float group_pick(bool mine, float v) { return __int_as_float(group_or_bits<G>(mine ? __float_as_int(v) : 0)); }
+template <int G>
+__device__ __forceinline__ double group_pick(bool mine, double v) {
+    const int lo = group_or_bits<G>(mine ? __double2loint(v) : 0), hi = group_or_bits<G>(mine ? __double2hiint(v) : 0);
+    return __hiloint2double(hi, lo);
+}
+
+// clip_row for the solves below: the same restriction of [L.lo, L.hi] as clip_row (sc_qp2.hpp), value for value, wherever the
+// lane's candidate can still be chosen.
+//   * "no restriction" is a quiet NaN operand of the max / min instead of -inf / +inf: the interval ends are never NaN on a lane
+//     with a finite foot point (clip_box leaves none for a unit direction), so max(lo, NaN) = lo = max(lo, -inf); a lane whose
+//     foot point is not finite ends with a non-finite cost and is masked either way.  One select per end instead of four.
+//   * a parallel row violated beyond tolerance sets L.lo = +inf in clip_row, which ends in t = inf or NaN, a non-finite point and
+//     a masked candidate; here it sets `dead`, and the caller masks the candidate.
+//   * a > eps is "not parallel and a >= 0", !(a >= -eps) is "not parallel and not a >= 0" (a NaN included, as in clip_row).
+// The dot products, the reciprocal and the quotient are clip_row's, operation for operation.
+template <typename T>
+__device__ __forceinline__ void clip_row_coop(LineQP<T>& L, bool& dead, T g0, T g1, T gc) {
+    const T a = g0 * L.d0 + g1 * L.d1;
+    const T r = g0 * L.p0 + (g1 * L.p1 + gc);
+    const bool pos = a > num<T>::eps_par();
+    const bool neg = !(a >= -num<T>::eps_par());
+    const bool par_viol = r < -num<T>::tol_feas() * max_abs_one_raw(gc);
+    const T q = r * rcp_(fabs_(a));
+    dead |= !pos && !neg && par_viol;
+    L.lo = max_neg_raw(L.lo, keep_or_nan(pos, q));
+    L.hi = min_raw(L.hi, keep_or_nan(neg, q));
+}
+
+// lowest lane of this lane's group that is set in a wave ballot: the group's byte (8 lanes) or half-word (16) of the mask
+template <int G>
+__device__ __forceinline__ bool group_first(unsigned long long m, int lane, int sub, bool& has) {
+    const unsigned bits = (unsigned)(m >> (lane & ~(G - 1))) & ((1u << G) - 1u);
+    has = bits != 0u;
+    return sub == __builtin_ctz(bits | (1u << G));               // bit G: an empty mask names no lane
+}
+
+template <typename TC, int... Xs>
+__device__ __forceinline__ void clip_partners8(LineQP<TC>& L, bool& dead, TC a0, TC a1, TC cc, std::integer_sequence<int, Xs...>) {
+    const TC m0 = dpp_mov<0x141>(a0), m1 = dpp_mov<0x141>(a1), mc = dpp_mov<0x141>(cc);
+    (clip_row_coop(L, dead, group_xor8<TC, Xs + 1>(a0, m0), group_xor8<TC, Xs + 1>(a1, m1), group_xor8<TC, Xs + 1>(cc, mc)), ...);
+}
+// what both solves do once the interval is known: the closest point of it, its cost, the group's cheapest candidate (lowest lane
+// on ties) and that lane's point
+template <typename TC, int G>
+__device__ __forceinline__ void coop_pick_winner(QpState<TC>& S, const LineQP<TC>& L, bool ok, int sub, int lane) {
     const TC inf = num<TC>::inf();
-    const bool testable = (sub < K) && !((a0 == TC(0)) && (a1 == TC(0)));     // all-zero rows are never projected on
-    LineQP<TC> L;
-    const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;       // S holds u_box; L: the line of this lane's row
-    if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;                   // wave-uniform: nothing violated anywhere
-    clip_box(L, k);
-    clip_partners8(L, a0, a1, cc, std::make_integer_sequence<int, 7>{});
     TC t = fmin_(fmax_(TC(0), L.lo), L.hi);
     const bool inverted = L.lo > L.hi;
     t = inverted ? TC(0.5) * (L.lo + L.hi) : t;                               // by a hair (rounding): split the difference, as the walk
@@ -154,58 +226,45 @@ __device__ __forceinline__ void coop_solve_all8(QpState<TC>& S, int K, int sub, 
     const TC v0 = L.p0 + t * L.d0, v1 = L.p1 + t * L.d1;
     const TC e0 = v0 - S.ur0, e1 = v1 - S.ur1;
     TC cost = e0 * e0 + e1 * e1;
-    cost = (viol && !empty && (cost == cost)) ? cost : inf;
-    const TC best = group_min<TC, 8>(cost);
-    const int gbase = lane & ~7;
-    const unsigned long long mg = __builtin_amdgcn_ballot_w64((cost == best) && (best < inf)) & (0xffull << gbase);
-    const bool has = mg != 0ull;
-    const int win = has ? (__builtin_ctzll(mg) - gbase) : -1;
-    const TC s0 = group_max<TC, 8>(sub == win ? v0 : -inf), s1 = group_max<TC, 8>(sub == win ? v1 : -inf);
+    cost = (ok && !empty && (cost == cost)) ? cost : inf;
+    TC best;
+    if constexpr (G == 8) best = min8_raw(cost); else best = min16_raw(cost);
+    bool has;
+    const bool mine = group_first<G>(__builtin_amdgcn_ballot_w64((cost == best) && (best < inf)), lane, sub, has);
+    const TC s0 = group_pick<G>(mine, v0), s1 = group_pick<G>(mine, v1);       // a finite cost means a finite point: its bits as they are
     S.u0 = has ? s0 : S.u0;                                                   // no candidate: u_box stays and fails the slack check
     S.u1 = has ? s1 : S.u1;
+}
+template <typename TC>
+__device__ __forceinline__ void coop_solve_all8(QpState<TC>& S, int K, int sub, int lane, TC a0, TC a1, TC cc,
+                                                const CbfConsts<TC>& k) {
+    const bool testable = (sub < K) && !((a0 == TC(0)) && (a1 == TC(0)));     // all-zero rows are never projected on
+    LineQP<TC> L;
+    const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;       // S holds u_box; L: the line of this lane's row
+    if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;                   // wave-uniform: nothing violated anywhere
+    clip_box(L, k);
+    bool dead = false;
+    clip_partners8(L, dead, a0, a1, cc, std::make_integer_sequence<int, 7>{});
+    coop_pick_winner<TC, 8>(S, L, viol && !dead, sub, lane);
 }
 
 // The same for 16 lanes per agent (K <= 16; one DPP row per agent): fifteen partners by row_ror, reductions by quad permutes and
 // the two mirrors.
-template <typename T>
-__device__ __forceinline__ T row_min16(T v) {
-    v = fmin_(v, dpp_mov<0xB1>(v)); v = fmin_(v, dpp_mov<0x4E>(v)); v = fmin_(v, dpp_mov<0x141>(v)); v = fmin_(v, dpp_mov<0x140>(v));
-    return v;
-}
-template <typename T>
-__device__ __forceinline__ T row_max16(T v) {
-    v = fmax_(v, dpp_mov<0xB1>(v)); v = fmax_(v, dpp_mov<0x4E>(v)); v = fmax_(v, dpp_mov<0x141>(v)); v = fmax_(v, dpp_mov<0x140>(v));
-    return v;
-}
 template <typename TC, int... Rs>
-__device__ __forceinline__ void clip_partners16(LineQP<TC>& L, TC a0, TC a1, TC cc, std::integer_sequence<int, Rs...>) {
-    (clip_row(L, dpp_mov<0x121 + Rs>(a0), dpp_mov<0x121 + Rs>(a1), dpp_mov<0x121 + Rs>(cc)), ...);     // row_ror:1 .. row_ror:15
+__device__ __forceinline__ void clip_partners16(LineQP<TC>& L, bool& dead, TC a0, TC a1, TC cc, std::integer_sequence<int, Rs...>) {
+    (clip_row_coop(L, dead, dpp_mov<0x121 + Rs>(a0), dpp_mov<0x121 + Rs>(a1), dpp_mov<0x121 + Rs>(cc)), ...);     // row_ror:1 .. row_ror:15
 }
 template <typename TC>
 __device__ __forceinline__ void coop_solve_all16(QpState<TC>& S, int K, int sub, int lane, TC a0, TC a1, TC cc,
                                                  const CbfConsts<TC>& k) {
-    const TC inf = num<TC>::inf();
     const bool testable = (sub < K) && !((a0 == TC(0)) && (a1 == TC(0)));
     LineQP<TC> L;
     const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;
     if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;
     clip_box(L, k);
-    clip_partners16(L, a0, a1, cc, std::make_integer_sequence<int, 15>{});
-    TC t = fmin_(fmax_(TC(0), L.lo), L.hi);
-    t = (L.lo > L.hi) ? TC(0.5) * (L.lo + L.hi) : t;
-    const bool empty = L.lo > L.hi + num<TC>::tol_feas() * fmax_(TC(1), fmax_(fabs_(L.lo), fabs_(L.hi)));
-    const TC v0 = L.p0 + t * L.d0, v1 = L.p1 + t * L.d1;
-    const TC e0 = v0 - S.ur0, e1 = v1 - S.ur1;
-    TC cost = e0 * e0 + e1 * e1;
-    cost = (viol && !empty && (cost == cost)) ? cost : inf;
-    const TC best = row_min16(cost);
-    const int gbase = lane & ~15;
-    const unsigned long long mg = __builtin_amdgcn_ballot_w64((cost == best) && (best < inf)) & (0xffffull << gbase);
-    const bool has = mg != 0ull;
-    const int win = has ? (__builtin_ctzll(mg) - gbase) : -1;
-    const TC s0 = row_max16(sub == win ? v0 : -inf), s1 = row_max16(sub == win ? v1 : -inf);
-    S.u0 = has ? s0 : S.u0;
-    S.u1 = has ? s1 : S.u1;
+    bool dead = false;
+    clip_partners16(L, dead, a0, a1, cc, std::make_integer_sequence<int, 15>{});
+    coop_pick_winner<TC, 16>(S, L, viol && !dead, sub, lane);
 }
 
 }  // namespace sc

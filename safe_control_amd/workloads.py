@@ -229,3 +229,41 @@ def kb_c3bf_fleet_scene(n_agents, n_moving=16, seed=0, spec=None, spacing=3.0, g
         obs[k, 3:5] = rng.uniform(-0.5, 0.5, 2)
         k += 1
     return X0, wps, obs
+
+
+CBFQP_STREAM_AGENTS = 203       # 25 groups of 8 lanes plus 3 agents: the last wave and the last group are partial
+
+
+def cbfqp_stream_cases(n=CBFQP_STREAM_AGENTS):
+    """Inputs of the bit-identity fixture tests/golden/cbfqp_stream_bits.npz (tools/record_cbfqp_stream_bits.py records it,
+    tests/test_cbfqp_stream_gpu.py replays it): the first `n` draws of du_cbfqp_batch(seed=0) at K = 8, 5, 1 and 16, in every
+    launch variant of the cooperative CBF-QP kernel.  Yields (name, io, compute, cbf_mode, X, u_ref, obs, n_obs) with float64
+    arrays; obs is [n, K, 7] or, for the shared table, [K, 7]."""
+    draws = {K: tuple(a[:n] for a in du_cbfqp_batch(4096, K, seed=0)) for K in (8, 5, 1, 16)}
+    rng = np.random.default_rng(203)
+    for K in (8, 5, 1, 16):
+        X, _, u_ref, obs = draws[K]
+        yield f"k{K}_f32c64", "f32", "f64", "cbf", X, u_ref, obs, None
+    for K in (8, 16):
+        X, _, u_ref, obs = draws[K]
+        yield f"k{K}_f64", "f64", "f64", "cbf", X, u_ref, obs, None
+        n_obs = rng.integers(0, K + 4, n).astype(np.int32)             # 0 and values above K included
+        n_obs[0], n_obs[1] = 0, K + 3
+        beyond = obs.copy()
+        for i in range(n):
+            beyond[i, min(int(n_obs[i]), K):] = 1e30                   # what lies beyond n_obs must be ignored
+        yield f"k{K}_nobs", "f32", "f64", "cbf", X, u_ref, beyond, n_obs
+    X, _, u_ref, obs = draws[8]
+    yield "k8_shared", "f32", "f64", "cbf", X, u_ref, obs[5].copy(), None
+    yield "k8_hard", "f32", "f64", "hard", X, u_ref, obs, None
+    sup = obs.copy()                                                   # every third agent: one superellipsoid among its circles
+    for i in range(0, n, 3):
+        r = sup[i, i % 8, 2]
+        sup[i, i % 8, 2:7] = [r + 0.3, 0.6 * r + 0.2, 4.0, 0.1 * (i % 11) - 0.5, 1.0]
+    yield "k8_superellipsoid", "f32", "f64", "cbf", X, u_ref, sup, None
+    odd = obs.copy()
+    Xo = X.copy()
+    odd[10, 3] = odd[10, 1]                                            # one duplicated row
+    odd[20, 4] = 0.0                                                   # one all-zero row
+    Xo[30, 0] = np.nan                                                 # one NaN state
+    yield "k8_degenerate", "f32", "f64", "cbf", Xo, u_ref, odd, None

@@ -1,5 +1,6 @@
 """GPU timing of the cooperative CBF-QP kernel inside a hipGraph (the headline launch shape): B agents, K obstacle rows (K <= 8: 8 lanes
-per agent, K <= 16: 16).  SC_EXP_LIB selects a variant build.    python3 tools/exp_coop_time.py [B K] ..."""
+per agent, K <= 16: 16).  SC_EXP_LIB selects a variant build; SC_EXP_NOBS=1 passes an n_obs tensor (all K), the launch of the closed loops.
+    python3 tools/exp_coop_time.py [B K] ..."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -16,20 +17,21 @@ for B, K in zip(args[0::2], args[1::2]):
     X, goal, ur, obs = W.du_cbfqp_batch(B, K, seed=0)
     t = lambda a: torch.tensor(a, dtype=torch.float32, device=dev)
     a, b, c = t(X), t(ur), t(obs)
+    nob = torch.full((B,), K, dtype=torch.int32, device=dev) if os.environ.get("SC_EXP_NOBS") == "1" else None
     out = (torch.empty((B, 2), dtype=torch.float32, device=dev), torch.empty((B,), dtype=torch.int32, device=dev),
            torch.empty((B, K), dtype=torch.float32, device=dev))
     s = torch.cuda.Stream()
     with torch.cuda.stream(s):
         for _ in range(3):
-            ctl.solve(a, b, c, out=out)
+            ctl.solve(a, b, c, nob, out=out)
         g = torch.cuda.CUDAGraph()
         n = 200
         with torch.cuda.graph(g, stream=s):
             for _ in range(n):
-                ctl.solve(a, b, c, out=out)
+                ctl.solve(a, b, c, nob, out=out)
         g.replay(); torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(s); g.replay(); e1.record(s)
         torch.cuda.synchronize()
-    print(os.environ.get("SC_EXP_LIB", "default"), f"B={B} K={K}", "%.2f us per launch" % (1e3 * e0.elapsed_time(e1) / n),
+    print(os.environ.get("SC_EXP_LIB", "default"), f"B={B} K={K}" + (" n_obs" if nob is not None else ""), "%.2f us per launch" % (1e3 * e0.elapsed_time(e1) / n),
           "optimal", int((out[1] == 0).sum()), "checksum", float(out[0].nan_to_num().double().sum()))
