@@ -7,10 +7,11 @@ obstacles while its barrier call expects one obstacle, so it cannot run as check
 (cvxpy -> GUROBI) is not installable.  Semantics restated here, for ONE obstacle (the nearest, row 0):
 
   variables   u (2), omega1, omega2                                            :57-60
-  objective   ||u - u_ref||^2 + p_sb1 (omega1 - 1)^2 + p_sb2 (omega2 - 1)^2      :72-76  (p_sb = 1e4, :21-24)
+  objective   ||u - u_ref||^2 + p_sb1 (omega1 - ref1)^2 + p_sb2 (omega2 - ref2)^2  :72-76  (p_sb = 1e4, references 1, :21-24)
   rel-deg 2   A u + b + (a1 + a2) omega1 h_dot + a1 a2 h omega2 >= 0             :83-90,105-115  (DU, KB, Quad2D; a1 = a2 = .5)
               A = dh_dot_dx g, b = dh_dot_dx f                                   :141-146
   rel-deg 1   A u + b + alpha h omega1 >= 0, objective without the omega2 term   :65-70,99-104 (C3BF; alpha = .5)
+              (omega2 meets no row and no cost there: it is reported at its reference, param["omega2"] or 1)
   bounds      |u0| <= a_max, |u1| <= w_max | beta_max; Quad2D f_min <= u <= f_max   :88-89,96-97,110-113
   no obstacle A = b = h = h_dot = 0                                              :133-137
 
@@ -103,5 +104,5 @@ def solve(model, X, u_ref, obs, spec, param=None):
     x, st = solve_diag_qp(D, r, G, c)
     if x is None:
         return dict(u=None, omega=None, status=st, h=h)
-    om = np.array([x[2], x[3] if rel2 else 1.0])
+    om = np.array([x[2], x[3] if rel2 else P.get("omega2", 1.0)])       # rel-degree 1: the inert omega2 stays at its reference
     return dict(u=x[:2], omega=om, status=st, h=h)

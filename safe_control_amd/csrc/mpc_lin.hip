@@ -355,7 +355,7 @@ __device__ __forceinline__ void lin_condense_mfma(const LinMem& W, const int N_r
 // issued back to back; with run-time bounds every multiply-add waits a full LDS round trip); NT > 0 (needs NX > 0): the
 // horizon too -- register Cholesky, lean LDS layout; KT > 0: obstacle rows.  0: run-time size.
 // OD: optimal decay on a relative-degree-1 model (BASELINE config 5's extension, oracle/od_mpc_rd1.py): one decay variable
-// rho_k per stage scales the gain of that stage's rows, h(b_k) - (1 - alpha rho_k) h(a_k) >= 0, at the price p_sb (rho_k - 1)^2;
+// rho_k per stage scales the gain of that stage's rows, h(b_k) - (1 - alpha rho_k) h(a_k) >= 0, at the price p_sb (rho_k - omega_ref)^2;
 // the input term is R u^2.  rho_k only meets the rows of stage k and enters them linearly, so its positive scalar block
 // D_k = 2 sf p_sb + sum_j sig_kj (alpha h(a_kj))^2 is eliminated in POINT space: Phi_k -= C_k C_k' / D_k on the 4 x 4 stage block,
 // the right-hand side loses G_k' C_k rr_k / D_k, and d rho_k = (rr_k - C_k' (G dz)_k) / D_k after the solve -- the condensed

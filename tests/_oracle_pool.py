@@ -19,20 +19,29 @@ MS_FAMILIES = {"du": "DynamicUnicycle2D", "uni": "Unicycle2D", "di": "DoubleInte
                "kb": "KinematicBicycle2D", "vtol": "VTOL2D", "vtol_od": "VTOL2D"}
 
 
-def ms_model(family, spec=None):
+def ms_model(family, spec=None, od=None, alpha1=None, alpha2=None):
     """The oracle model of `family` built from the completed robot_spec the kernel gets (safe_control_amd.robots.spec), not from the
-    model's own defaults: every limit and radius is the host class's."""
+    model's own defaults: every limit and radius is the host class's.  `od` = dict(omega_ref=(w1, w2), p_sb=(p1, p2)) and the two gains
+    replace those of the optimal-decay model ("vtol_od")."""
     from oracle import ms_ipopt as MS
     from safe_control_amd.robots.spec import complete_robot_spec
     mk = {"du": MS.du_model, "uni": MS.uni_model, "di": MS.di_model, "si": MS.si_model, "kb": MS.kb_model,
           "vtol": MS.vtol_model, "vtol_od": MS.vtol_od_model}[family]
     sp = complete_robot_spec(dict(spec or {}, model=MS_FAMILIES[family]))
     keys = mk()["spec"].keys()
-    return mk({k: v for k, v in sp.items() if k in keys})
+    mdl = mk({k: v for k, v in sp.items() if k in keys})
+    if od is not None:
+        mdl["od"] = dict(omega_ref=np.asarray(od["omega_ref"], dtype=np.float64), p_sb=np.asarray(od["p_sb"], dtype=np.float64))
+    if alpha1 is not None:
+        mdl["alpha1"] = float(alpha1)
+    if alpha2 is not None:
+        mdl["alpha2"] = float(alpha2)
+    return mdl
 
 
 def _worker_ms(d, outp):
-    """kind = "ms:<family>": oracle.ms_ipopt.solve with params dict(opts=<profile>, N=<horizon or None>, spec=<robot_spec>); per row
+    """kind = "ms:<family>": oracle.ms_ipopt.solve with params dict(opts=<profile>, N=<horizon or None>, spec=<robot_spec>, od=<decay
+    references and penalties or None>, alpha1, alpha2); per row
     u, st, it, plan (X then U, flattened), exit (index into ms_ipopt.EXITS), filter_peak, resto (restoration phases entered),
     resto_iters, f, and the first TRACE_ROWS rows of the iterate trace [E0, dinf, pinf, comp, mu, theta, delta_w, alpha] (NaN past
     the end; ntr rows in all; the restoration's rows carry -alpha and resto_row = 1)."""
@@ -41,7 +50,7 @@ def _worker_ms(d, outp):
     X, up, goal, obs = d["X"], d["up"], d["goal"], d["obs"]
     prm = d["params"].item() if "params" in d.files else {}
     prm = dict(prm or {})
-    mdl = ms_model(fam, prm.get("spec"))
+    mdl = ms_model(fam, prm.get("spec"), prm.get("od"), prm.get("alpha1"), prm.get("alpha2"))
     opts, N = dict(prm.get("opts") or MS.KERNEL_PROFILE), prm.get("N")
     B = X.shape[0]
     out = {k: [] for k in ("u", "st", "it", "plan", "exit", "filter_peak", "resto", "resto_iters", "f", "trace", "resto_row", "ntr")}
@@ -60,13 +69,14 @@ def _worker_ms(d, outp):
     np.savez(outp, **{k: np.array(v) for k, v in out.items()})
 
 
-def ms_solve_many(family, X, up, goal, obs, opts=None, N=None, spec=None, workers=None, timeout=1800):
+def ms_solve_many(family, X, up, goal, obs, opts=None, N=None, spec=None, workers=None, timeout=1800, od=None, alpha1=None, alpha2=None):
     """oracle.ms_ipopt.solve with the model of `family` (ms_model) on every row (obs [B,K,7] or one shared [K,7] table); dict of
     arrays, see _worker_ms; exit as the names of ms_ipopt.EXITS."""
     from oracle import ms_ipopt as MS
     B = X.shape[0]
     ob = obs if obs.ndim == 3 else np.broadcast_to(obs, (B,) + obs.shape)
-    r = _run(dict(kind=np.array("ms:" + family)), X, up, goal, np.ascontiguousarray(ob), dict(opts=opts, N=N, spec=spec), workers, timeout)
+    r = _run(dict(kind=np.array("ms:" + family)), X, up, goal, np.ascontiguousarray(ob),
+             dict(opts=opts, N=N, spec=spec, od=od, alpha1=alpha1, alpha2=alpha2), workers, timeout)
     r["exit"] = np.array(MS.EXITS)[r["exit"]]
     return r
 
@@ -133,6 +143,47 @@ def _worker_od_rd1(d, outp):
         u[i], _, st[i], it[i], info = O.solve(X[i], up[i], goal[i], obs[i], P, return_info=True)
         z[i], rho[i], f[i] = info["z"], info["rho"], info["f"]
     np.savez(outp, u=u, st=st, it=it, z=z, rho=rho, f=f)
+
+
+def _worker_od_du(d, outp):
+    """kind = "od_du": oracle.od_mpc_cbf.solve (DynamicUnicycle2D); params = overrides of its DEFAULTS (N, alpha1, .., p_sb2)."""
+    from oracle import od_mpc_cbf as O
+    X, up, goal, obs = d["X"], d["up"], d["goal"], d["obs"]
+    over = dict((d["params"].item() if "params" in d.files else {}) or {})
+    N = over.get("N", O.DEFAULTS["N"])
+    B = X.shape[0]
+    u = np.zeros((B, 2)); st = np.zeros(B, dtype=np.int64); it = np.zeros(B, dtype=np.int64)
+    z = np.zeros((B, 2 * N)); rho = np.zeros((B, 2 * N)); f = np.zeros(B); err = np.zeros(B)
+    for i in range(B):
+        u[i], _, st[i], it[i], info = O.solve(X[i], up[i], goal[i], obs[i], params=over, return_info=True)
+        z[i], rho[i], f[i], err[i] = info["zz"][: 2 * N], info["zz"][2 * N:], info["f"], info["err"]
+    np.savez(outp, u=u, st=st, it=it, z=z, rho=rho, f=f, err=err)
+
+
+def _worker_od_gn(d, outp):
+    """kind = "od_gn:kb" | "od_gn:quad2d": oracle.od_mpc_gn.solve; params = N and overrides of od_mpc_gn.params (alpha1, .., p_sb2)."""
+    from oracle import od_mpc_gn as OG
+    mdl = {"kb": OG.kb_model, "quad2d": OG.quad2d_model}[str(d["kind"])[6:]]()
+    X, up, goal, obs = d["X"], d["up"], d["goal"], d["obs"]
+    over = dict((d["params"].item() if "params" in d.files else {}) or {})
+    N = over.pop("N", 10)
+    B = X.shape[0]
+    u = np.zeros((B, 2)); st = np.zeros(B, dtype=np.int64); it = np.zeros(B, dtype=np.int64)
+    z = np.zeros((B, 2 * N)); rho = np.zeros((B, 2 * N)); f = np.zeros(B); err = np.zeros(B)
+    for i in range(B):
+        u[i], _, st[i], it[i], info = OG.solve(mdl, X[i], up[i], goal[i], obs[i], N=N, params_over=over, return_info=True)
+        z[i], rho[i], f[i], err[i] = info["zz"][: 2 * N], info["zz"][2 * N:], info["f"], info["err"]
+    np.savez(outp, u=u, st=st, it=it, z=z, rho=rho, f=f, err=err)
+
+
+def od_du_solve_many(X, up, goal, obs, params=None, workers=None, timeout=1800):
+    """oracle.od_mpc_cbf.solve on every row; dict(u, st, it, z, rho (omega1_k, omega2_k per stage), f, err)."""
+    return _run(dict(kind=np.array("od_du")), X, up, goal, obs, params, workers, timeout)
+
+
+def od_gn_solve_many(family, X, up, goal, obs, params=None, workers=None, timeout=1800):
+    """oracle.od_mpc_gn.solve with the model of `family` ("kb" | "quad2d") on every row; dict(u, st, it, z, rho, f, err)."""
+    return _run(dict(kind=np.array("od_gn:" + family)), X, up, goal, obs, params, workers, timeout)
 
 
 def _worker_od_vtol(d, outp):
@@ -227,8 +278,14 @@ def _worker(inp, outp):
     d = np.load(inp, allow_pickle=True)
     if "kind" in d.files and str(d["kind"]) == "odvtol":
         return _worker_od_vtol(d, outp)
-    if "kind" in d.files and str(d["kind"]).startswith("od_"):
+    if "kind" in d.files and str(d["kind"]) == "od_du":
+        return _worker_od_du(d, outp)
+    if "kind" in d.files and str(d["kind"]).startswith("od_gn:"):
+        return _worker_od_gn(d, outp)
+    if "kind" in d.files and str(d["kind"]) in ("od_uni", "od_quad3d"):
         return _worker_od_rd1(d, outp)
+    if "kind" in d.files and str(d["kind"]).startswith("od_"):
+        raise ValueError(f"unknown optimal-decay oracle kind {d['kind']}")
     if "kind" in d.files and str(d["kind"]).startswith("p1:"):
         return _worker_phase1(d, outp)
     if "kind" in d.files and str(d["kind"]).startswith("fam:"):
@@ -255,6 +312,17 @@ def mpc_cbf_solve_many(X, up, goal, obs, params=None, workers=None, timeout=900)
     """oracle.mpc_cbf.solve on every row; returns (u0[B,2], status[B], iters[B], z[B,n], f[B])."""
     r = _run({}, X, up, goal, obs, params, workers, timeout)
     return r["u"], r["st"], r["it"], r["z"], r["f"]
+
+
+def concurrently(jobs):
+    """Several *_solve_many calls at once, MAX_WORKERS child processes between them: jobs = [(function, args, kwargs), ...]; their
+    results in that order.  (One oracle run per parameter set of a batch: the runs are short and a batch of 32 fills few workers.)  The cap
+    of MAX_WORKERS processes holds as long as no two calls of this function overlap: call it from one thread only."""
+    from concurrent.futures import ThreadPoolExecutor
+    w = max(1, MAX_WORKERS // len(jobs))
+    with ThreadPoolExecutor(len(jobs)) as ex:
+        futs = [ex.submit(fn, *a, **dict(kw, workers=w)) for fn, a, kw in jobs]
+        return [f.result() for f in futs]
 
 
 def _run(extra, X, up, goal, obs, params, workers, timeout):
