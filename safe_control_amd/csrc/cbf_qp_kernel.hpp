@@ -346,12 +346,175 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TI
     }
 }
 
+// ======================================================================================
+// The cooperative kernel above specialised for the headline launch: DynamicUnicycle2D, f64 arithmetic, exactly 8 rows per
+// agent, per-agent obstacles, no n_obs.  The generic kernel decides all of that at run time inside every wave; a lone wave per
+// SIMD pays for each executed instruction, so what the host knows before the launch is a template parameter or is
+// absent here:
+//   * K = 8 = lanes per agent: every lane has a row, every row is used (no has_row, no nk clamp, no selects of a0 / a1 / cc / h);
+//   * offsets are 32-bit: lane `slot` = blockIdx * 64 + lane owns row `slot` of obs[B, 8, 7] and entry `slot` of h_out[B, 8]
+//     (launch_coop checks that the byte offsets fit);
+//   * FULL: B is a multiple of the 8 agents of a wave, so there is no `active` guard at all; !FULL keeps it (c.B);
+//   * HAS_H: h_out is non-null;
+//   * the obstacle row arrives with two loads (16 + 12 bytes, f32 storage) instead of seven;
+//   * the f64 sincos reads its sixteen constants, and clip_box its `lo - tol` / `hi + tol`, from the argument block.
+// Arithmetic and its order are those of the generic kernel, so both return the same bits (tests/test_cbfqp_special_gpu.py).
+// Six pointers in order of first use are preloaded (12 dwords); n_obs, B, K and obs_shared are not arguments.
+// The constants travel as four 64-byte vectors so that a wave fetches them with four scalar loads (field by field the compiler
+// emits one load per double: two dozen executed instructions).  Filled by launch_coop8_du, taken apart at the top of the kernel.
+typedef double sc_d8 __attribute__((ext_vector_type(8)));
+struct Coop8Consts {
+    sc_d8 t0;                                              // SinCosTab: two_over_pi, pio2_1, pio2_2, pio2_3, s[0..3]
+    sc_d8 t1;                                              //            s[4], s[5], c[0..5]
+    sc_d8 k0;                                              // R, g1, g2, inv_dt, inv_dt2, lo0, hi0, lo1
+    sc_d8 k1;                                              // hi1, BoxTol: lo0, hi0, lo1, hi1; three spare
+    int hard;
+    unsigned B;                                            // read by the !FULL instantiations only
+};
+
+// normalise_row with the sum of squares written as the fused form the generic kernel compiles to.  `n0 * n0 + n1 * n1` leaves it to
+// the compiler which product stays a rounded multiply and which goes into the FMA; behind the generic kernel's `used` selects it
+// picks fma(n1, n1, n0 * n0), without them (here) the other one, and the two differ in the last bit of some rows.
+__device__ __forceinline__ void normalise_row_as_generic(double& n0, double& n1, double& c, double& poison) {
+    const double nn = __builtin_fma(n1, n1, n0 * n0);
+    poison += 0.0 * (nn + c);
+    const double inv = nn > 0.0 ? rsqrt_(nn) : 1.0;
+    n0 *= inv; n1 *= inv; c *= inv;
+}
+
+template <typename TIO, bool FULL, bool HAS_H>
+__global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
+                                                            const TIO* __restrict__ u_ref, TIO* __restrict__ u_out,
+                                                            TIO* __restrict__ h_out, int* __restrict__ status_out,
+                                                            const Coop8Consts c) {
+#ifdef SC_EXP_EMPTY
+    return;
+#endif
+    using TC = double;
+    using V2 = typename vec2<TIO>::type;
+    const unsigned lane = threadIdx.x;
+    const unsigned sub = lane & 7u;
+    const unsigned slot = blockIdx.x * 64u + lane;         // agent * 8 + sub
+    const unsigned agent = slot >> 3;
+    bool active = true;
+    if constexpr (!FULL) active = agent < c.B;
+    const unsigned row_i = active ? slot : sub;            // inactive lanes compute on agent 0, store nothing
+    const unsigned ag_i = row_i >> 3;
+
+    struct { TIO v[7]; } orow;
+    __builtin_memcpy(&orow, obs + row_i * 7u, sizeof(orow));
+    const V2 ur = reinterpret_cast<const V2*>(u_ref)[ag_i];
+    const StateRow<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D> xs = load_state<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(X, ag_i);
+    fetch_arg_now(c.t0); fetch_arg_now(c.t1); fetch_arg_now(c.k0); fetch_arg_now(c.k1); fetch_arg_now(c.hard);
+
+    SinCosTab sc;
+    sc.two_over_pi = c.t0[0]; sc.pio2_1 = c.t0[1]; sc.pio2_2 = c.t0[2]; sc.pio2_3 = c.t0[3];
+    sc.s[0] = c.t0[4]; sc.s[1] = c.t0[5]; sc.s[2] = c.t0[6]; sc.s[3] = c.t0[7]; sc.s[4] = c.t1[0]; sc.s[5] = c.t1[1];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) sc.c[i] = c.t1[2 + i];
+    CbfConsts<TC> k;                                       // the fields cbf_row<DynamicUnicycle2D> and the solve read; the rest is never looked at
+    k.R = c.k0[0]; k.a1 = TC(0); k.a2 = TC(0); k.g1 = c.k0[1]; k.g2 = c.k0[2]; k.inv_dt = c.k0[3]; k.inv_dt2 = c.k0[4];
+    k.lo0 = c.k0[5]; k.hi0 = c.k0[6]; k.lo1 = c.k0[7]; k.hi1 = c.k1[0]; k.inv_Lr = TC(0); k.inv_mass = TC(1); k.hard = c.hard;
+    BoxTol<TC> bt;
+    bt.lo0 = c.k1[1]; bt.hi0 = c.k1[2]; bt.lo1 = c.k1[3]; bt.hi1 = c.k1[4];
+
+    const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
+    Agent<TC> ag;                                          // make_agent with the constants of its sincos from the argument block
+    ag.x = TC(xs.v[0]); ag.y = TC(xs.v[1]); ag.th = TC(xs.v[2]); ag.v = TC(xs.v[3]);
+    sincos_tab(ag.th, sc, &ag.s, &ag.c);
+    ag.f0 = ag.v * ag.c;
+    ag.f1 = ag.v * ag.s;
+
+    // ---- this lane's row -------------------------------------------------------------------
+    TC o[7];
+#pragma unroll
+    for (int f = 0; f < 7; ++f) o[f] = TC(orow.v[f]);
+    TC h, a0, a1, cc;
+    const bool ok = cbf_row<TC, SC_MODEL_DYNAMIC_UNICYCLE2D, false>(ag, o, k, a0, a1, cc, h);
+    const bool bad_mine = !ok;
+    if constexpr (HAS_H) {
+        if (active) h_out[slot] = TIO(h);
+    }
+    TC poison = TC(0);
+    normalise_row_as_generic(a0, a1, cc, poison);
+
+    // ---- the solve, the slack check and the outputs: as in cbfqp_coop_kernel ------------------
+    QpState<TC> S;
+    qp_begin(S, ur0, ur1, k);
+    coop_solve_all8_full<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, bt);
+    qp_finish_box(S, k);
+    TC worst = qp_row_margin(num<TC>::inf(), a0, a1, cc, S.u0, S.u1, poison);
+    const bool nan_mine = !(poison == poison);
+    worst = nan_mine ? -num<TC>::inf() : worst;
+    worst = min8_raw(worst);
+    const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
+    const bool bad_any = ((bad_mask >> (lane & ~7u)) & 0xffull) != 0ull;
+    int st = qp_status(S, worst, TC(0), k);
+    if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
+    TC u0 = S.u0, u1 = S.u1;
+    if (st != SC_STATUS_OPTIMAL) { u0 = num<TC>::nan(); u1 = num<TC>::nan(); }
+    if (active && sub == 0) {
+        V2 uo; uo.x = TIO(u0); uo.y = TIO(u1);
+        reinterpret_cast<V2*>(u_out)[agent] = uo;
+        status_out[agent] = st;
+    }
+}
+
+// Developer builds only (tools/README.md): -DSC_EXP_GRID=n launches n workgroups whatever the batch, to time the wave-launch ramp
+// of an empty node.  Only a kernel without a body may run on a grid that is not the batch's.
+#if defined(SC_EXP_GRID) && !defined(SC_EXP_EMPTY)
+#error "SC_EXP_GRID needs SC_EXP_EMPTY: a kernel with a body would run past the batch"
+#endif
+static inline unsigned coop_grid(unsigned nblk) {
+#ifdef SC_EXP_GRID
+    return SC_EXP_GRID;
+#else
+    return nblk;
+#endif
+}
+
+// SC_CBFQP_GENERIC=1: every launch takes the generic kernels (the reference of tests/test_cbfqp_special_gpu.py; the kill switch)
+static inline bool sc_cbfqp_generic() {
+    static const bool v = [] { const char* e = getenv("SC_CBFQP_GENERIC"); return e && e[0] == '1'; }();
+    return v;
+}
+
+template <typename TIO>
+static hipError_t launch_coop8_du(const sc_cbfqp_params& p, long long B, const void* X, const void* u_ref, const void* obs,
+                                  void* u_out, int* status, void* h_out, hipStream_t stream) {
+    const CbfConsts<double> k = make_consts<double>(p);   // once per launch, on the host
+    const BoxTol<double> bt = box_tol(k);
+    const SinCosTab t = make_sincos_tab();
+    Coop8Consts c;
+    c.t0 = sc_d8{t.two_over_pi, t.pio2_1, t.pio2_2, t.pio2_3, t.s[0], t.s[1], t.s[2], t.s[3]};
+    c.t1 = sc_d8{t.s[4], t.s[5], t.c[0], t.c[1], t.c[2], t.c[3], t.c[4], t.c[5]};
+    c.k0 = sc_d8{k.R, k.g1, k.g2, k.inv_dt, k.inv_dt2, k.lo0, k.hi0, k.lo1};
+    c.k1 = sc_d8{k.hi1, bt.lo0, bt.hi0, bt.lo1, bt.hi1, 0.0, 0.0, 0.0};
+    c.hard = k.hard;
+    c.B = (unsigned)B;
+    const dim3 grid(coop_grid((unsigned)((B + 7) / 8))), block(64);
+#define SC_GO(FULL, HAS_H)                                                                                             \
+    hipLaunchKernelGGL((cbfqp_coop8_du_kernel<TIO, FULL, HAS_H>), grid, block, 0, stream, (const TIO*)obs, (const TIO*)X, \
+                       (const TIO*)u_ref, (TIO*)u_out, (TIO*)h_out, status, c)
+    if (B % 8 == 0) { if (h_out) SC_GO(true, true); else SC_GO(true, false); }
+    else { if (h_out) SC_GO(false, true); else SC_GO(false, false); }
+#undef SC_GO
+    return hipGetLastError();
+}
+
 template <typename TIO, typename TC, int G, int MODEL>
 static hipError_t launch_coop(const sc_cbfqp_params& p, long long B, int K, const void* X, const void* u_ref,
                               const void* obs, const int* n_obs, void* u_out, int* status, void* h_out,
                               hipStream_t stream) {
+    // The specialised kernel serves the launches it was written for and nothing else: 8 rows of per-agent obstacles, no n_obs, a
+    // batch in the cooperative regime, and every byte offset below 2^31 (the obstacle block is the largest array of a launch).
+    if constexpr (G == 8 && MODEL == SC_MODEL_DYNAMIC_UNICYCLE2D && sizeof(TC) == 8 && SC_COOP_WAVES == 1) {
+        if (K == 8 && n_obs == nullptr && p.obs_shared == 0 && B >= 1 && B <= sc_coop_max_agents() &&
+            B * 8 * 7 * (long long)sizeof(TIO) <= 0x7fffffffLL && !sc_cbfqp_generic())
+            return launch_coop8_du<TIO>(p, B, X, u_ref, obs, u_out, status, h_out, stream);
+    }
     constexpr int APW = 64 / G;
-    const unsigned nblk = (unsigned)((B + APW * SC_COOP_WAVES - 1) / (APW * SC_COOP_WAVES));
+    const unsigned nblk = coop_grid((unsigned)((B + APW * SC_COOP_WAVES - 1) / (APW * SC_COOP_WAVES)));
     const CbfConsts<TC> k = make_consts<TC>(p);           // once per launch, on the host: the kernel gets the finished constants
     hipLaunchKernelGGL((cbfqp_coop_kernel<TIO, TC, G, MODEL>), dim3(nblk), dim3(64 * SC_COOP_WAVES), 0, stream,
                        (const TIO*)obs, (const TIO*)X, (const TIO*)u_ref, n_obs, B, K, (int)p.obs_shared,

@@ -248,6 +248,55 @@ __device__ __forceinline__ void coop_solve_all8(QpState<TC>& S, int K, int sub, 
     coop_pick_winner<TC, 8>(S, L, viol && !dead, sub, lane);
 }
 
+// ---- the solve of the specialised K = 8 kernel (cbfqp_coop8_du_kernel) ---------------------------------------------------
+// clip_box with `lo - tol` and `hi + tol` handed in: the box is wave-uniform and there is no scalar f64 arithmetic on gfx950, so
+// clip_box derives the four sums with vector adds in every wave.  The host computes them with the same two IEEE operations on
+// the same values (box_tol), so `inside` is decided on the same bits.  Everything else is clip_box, line for line.
+template <typename T>
+struct BoxTol { T lo0, hi0, lo1, hi1; };                  // lo0 - tol_feas, hi0 + tol_feas, lo1 - tol_feas, hi1 + tol_feas
+template <typename T>
+__host__ __device__ inline BoxTol<T> box_tol(const CbfConsts<T>& k) {
+    const T tol = sizeof(T) == 8 ? T(1e-9) : T(1e-5f);     // num<T>::tol_feas(), which is device-only
+    BoxTol<T> b;
+    b.lo0 = k.lo0 - tol; b.hi0 = k.hi0 + tol; b.lo1 = k.lo1 - tol; b.hi1 = k.hi1 + tol;
+    return b;
+}
+template <typename T>
+__device__ __forceinline__ void clip_box_tol(LineQP<T>& L, const CbfConsts<T>& k, const BoxTol<T>& bt) {
+    const T inf = num<T>::inf();
+    {
+        const T r = rcp_(L.d0);
+        const T t1 = (k.lo0 - L.p0) * r, t2 = (k.hi0 - L.p0) * r;
+        const bool flat = L.d0 == T(0);
+        const bool inside = (L.p0 >= bt.lo0) && (L.p0 <= bt.hi0);
+        const T lo = flat ? (inside ? -inf : inf) : fmin_(t1, t2);
+        const T hi = flat ? inf : fmax_(t1, t2);
+        L.lo = lo; L.hi = hi;
+    }
+    {
+        const T r = rcp_(L.d1);
+        const T t1 = (k.lo1 - L.p1) * r, t2 = (k.hi1 - L.p1) * r;
+        const bool flat = L.d1 == T(0);
+        const bool inside = (L.p1 >= bt.lo1) && (L.p1 <= bt.hi1);
+        const T lo = flat ? (inside ? -inf : inf) : fmin_(t1, t2);
+        const T hi = flat ? inf : fmax_(t1, t2);
+        L.lo = fmax_(L.lo, lo); L.hi = fmin_(L.hi, hi);
+    }
+}
+// coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`) and the box bounds above
+template <typename TC>
+__device__ __forceinline__ void coop_solve_all8_full(QpState<TC>& S, int sub, int lane, TC a0, TC a1, TC cc,
+                                                     const CbfConsts<TC>& k, const BoxTol<TC>& bt) {
+    const bool testable = !((a0 == TC(0)) && (a1 == TC(0)));
+    LineQP<TC> L;
+    const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;
+    if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;
+    clip_box_tol(L, k, bt);
+    bool dead = false;
+    clip_partners8(L, dead, a0, a1, cc, std::make_integer_sequence<int, 7>{});
+    coop_pick_winner<TC, 8>(S, L, viol && !dead, sub, lane);
+}
+
 // The same for 16 lanes per agent (K <= 16; one DPP row per agent): fifteen partners by row_ror, reductions by quad permutes and
 // the two mirrors.
 template <typename TC, int... Rs>

@@ -50,6 +50,50 @@ __device__ __forceinline__ void sincos_(double x, double* s, double* c) {
     *s = (n & 2) ? -sv : sv;
     *c = ((n + 1) & 2) ? -cv : cv;
 }
+// The same f64 sincos with its constants handed in instead of written as literals.  A kernel that takes a SinCosTab by value
+// reads the sixteen doubles as scalar operands of the FMAs (one scalar operand per VOP3 instruction on gfx9: the first Horner
+// step of each polynomial names two, so one of them still goes through a VGPR) where the literals above cost a pair of v_mov
+// each, in every wave.  make_sincos_tab() fills the block on the host from the literals of sincos_ above; the operations and
+// their order are those of sincos_, so the two return the same bits.
+struct SinCosTab {
+    double two_over_pi, pio2_1, pio2_2, pio2_3;            // Cody-Waite: 2 / pi and the three parts of pi / 2
+    double s[6];                                           // __kernel_sin, highest power first (S6 .. S1)
+    double c[6];                                           // __kernel_cos, highest power first (C6 .. C1)
+};
+__host__ __device__ inline SinCosTab make_sincos_tab() {
+    SinCosTab t;
+    t.two_over_pi = 0.63661977236758138;
+    t.pio2_1 = 1.5707963267948966; t.pio2_2 = 6.123233995736766e-17; t.pio2_3 = -1.4973849048591698e-33;
+    t.s[0] = 1.58969099521155010221e-10; t.s[1] = -2.50507602534068634195e-08; t.s[2] = 2.75573137070700676789e-06;
+    t.s[3] = -1.98412698298579493134e-04; t.s[4] = 8.33333333332248946124e-03; t.s[5] = -1.66666666666666324348e-01;
+    t.c[0] = -1.13596475577881948265e-11; t.c[1] = 2.08757232129817482790e-09; t.c[2] = -2.75573143513906633035e-07;
+    t.c[3] = 2.48015872894767294178e-05; t.c[4] = -1.38888888888741095749e-03; t.c[5] = 4.16666666666666019037e-02;
+    return t;
+}
+__device__ __forceinline__ void sincos_tab(double x, const SinCosTab& t, double* s, double* c) {
+    if (!(fabs(x) < 1.0e5)) { sincos(x, s, c); return; }
+    const double k = rint(x * t.two_over_pi);
+    double r = __builtin_fma(-k, t.pio2_1, x);
+    r = __builtin_fma(-k, t.pio2_2, r);
+    r = __builtin_fma(-k, t.pio2_3, r);
+    const double z = r * r;
+    double ps = __builtin_fma(z, t.s[0], t.s[1]);
+    ps = __builtin_fma(z, ps, t.s[2]);
+    ps = __builtin_fma(z, ps, t.s[3]);
+    ps = __builtin_fma(z, ps, t.s[4]);
+    const double ks = __builtin_fma(z * r, __builtin_fma(z, ps, t.s[5]), r);
+    double pc = __builtin_fma(z, t.c[0], t.c[1]);
+    pc = __builtin_fma(z, pc, t.c[2]);
+    pc = __builtin_fma(z, pc, t.c[3]);
+    pc = __builtin_fma(z, pc, t.c[4]);
+    pc = __builtin_fma(z, pc, t.c[5]);
+    const double hz = 0.5 * z, w = 1.0 - hz;
+    const double kc = w + (((1.0 - w) - hz) + z * (z * pc));
+    const int n = (int)k & 3;
+    const double sv = (n & 1) ? kc : ks, cv = (n & 1) ? ks : kc;
+    *s = (n & 2) ? -sv : sv;
+    *c = ((n + 1) & 2) ? -cv : cv;
+}
 __device__ __forceinline__ float sqrt_(float x) { return sqrtf(x); }
 __device__ __forceinline__ double sqrt_(double x) { return sqrt(x); }
 __device__ __forceinline__ float fabs_(float x) { return fabsf(x); }
