@@ -690,8 +690,10 @@ int sc_neighbor_obstacles_batch_ws(int32_t io_dtype, int64_t B_all, int64_t firs
  * rotate_to), CBFQP.solve_control_problem, collision checks (:445-495, :627-646), robot.step (:637)
  * and the return code (:666-668).  Agent state stays in registers between steps.
  * Models: DynamicUnicycle2D, Unicycle2D, the KinematicBicycle2D family, and SingleIntegrator2D / DoubleIntegrator2D with
- * enable_rotation = 0 (their rotate state runs the attitude controllers, which are outside this library; without them the
+ * enable_rotation = 0 (their rotate state runs the attitude controllers, which this entry point does not have; without them the
  * heading of an integrator never changes and only decides the first state-machine state, which the caller sets).
+ * sc_tracking_sense_rollout_batch below is the loop with the integrators' heading, the 'simple' and 'velocity_tracking_yaw'
+ * attitude controllers and FOV sensing of unknown obstacles.
  */
 #define SC_SM_IDLE   0
 #define SC_SM_TRACK  1
@@ -781,6 +783,57 @@ int sc_tracking_fleet_step_batch(const sc_tracking_params* params, int64_t B_loc
 #define SC_FLEET_MAX_NEIGHBOURS 32
 #define SC_FLEET_MAX_TABLE      32
 #define SC_FLEET_MAX_ROWS       64   /* M + K_nb */
+
+/* ---- closed-loop control_step with FOV sensing of unknown obstacles and yaw control -----------------------
+ * sc_tracking_rollout_batch plus the three parts of LocalTrackingController.control_step it leaves out:
+ *   unknown obstacles  a second table unknown_table [n_unknown,7] (tracking.py:277-293) whose rows the agent does not know
+ *                      until its camera cone touches them ('fov' detection, utils/detection.py:28-87, every step after the
+ *                      goal update, tracking.py:580).  A sighted row joins the CBF-QP's candidates behind the known rows as
+ *                      the circle [x, y, r, 0, 0, 0, 0], r = o[2], or max(o[2], o[3], 0) when o[6] >= 0.5.  persistent = 1:
+ *                      sighted rows are remembered for good (robots/robot.py:810-826); 0: the candidates are the rows sighted
+ *                      in this step.  EVERY unknown row, sighted or not, counts in the two collision tests as the circle of
+ *                      radius o[2] (tracking.py:451-460).
+ *   the heading of SingleIntegrator2D / DoubleIntegrator2D: yaw [B] and u_att [B] (NaN = the reference's None) beside the
+ *                      state; 'rotate' turns yaw at clip(2 wrap(goal_angle - yaw), +-w_max) and brakes (tracking.py:592-594),
+ *                      leaves when |yaw - goal_angle| <= rotation_threshold and drops u_att (:506-521); in 'track' u_att comes
+ *                      from the attitude controller after the solve (:621-624): SC_ATT_SIMPLE the constant simple_yaw_rate,
+ *                      SC_ATT_VELOCITY_TRACKING_YAW clip(att_kp wrap(atan2(vy, vx) - yaw), +-w_max) for v = u (single) or
+ *                      X[2:4] + att_preview_time u (double integrator), 0 when |v| < 1e-2; a taken step ends with
+ *                      yaw = wrap(yaw + u_att dt) unless u_att is NaN (robots/robot.py:441-448).
+ *   DynamicUnicycle2D looks along X[2]; att_type must be SC_ATT_NONE for it and yaw / u_att may be NULL.
+ * Not built (they need polygon geometry): 'ray' detection, sensing footprints and return code 1, the 'visibility_*' and
+ * 'gatekeeper' attitude controllers.  Both tables are static (params->dyn_obs = 0); n_unknown <= SC_SENSE_MAX_UNKNOWN.
+ */
+#define SC_ATT_NONE                  0
+#define SC_ATT_SIMPLE                1
+#define SC_ATT_VELOCITY_TRACKING_YAW 2
+#define SC_SENSE_MAX_UNKNOWN         64
+
+typedef struct sc_sense_params {
+    int32_t n_unknown;         /* Mu: rows of unknown_table, 0..SC_SENSE_MAX_UNKNOWN                               */
+    int32_t persistent;        /* robot_spec['unknown_obs_persistent_fov'] (True)                                   */
+    int32_t att_type;          /* SC_ATT_*                                                                          */
+    int32_t reserved;          /* keep 0                                                                            */
+    double  fov_angle;         /* radians (robot_spec['fov_angle'] = 70 degrees, robots/robot.py:53-54)             */
+    double  cam_range;         /* robot_spec['cam_range'] = 3.0                                                     */
+    double  w_max;             /* robot_spec['w_max'] = 0.5: bound of the yaw rate                                  */
+    double  att_kp;            /* robot_spec['velocity_tracking_yaw_kp'] = 1.5                                      */
+    double  att_preview_time;  /* robot_spec['velocity_tracking_yaw_preview_time'] = 0.0                            */
+    double  simple_yaw_rate;   /* robot_spec['simple_yaw_rate'] = w_max                                             */
+} sc_sense_params;
+
+/* Arguments as sc_tracking_rollout_batch, and: unknown_table [n_unknown,7] (io_dtype); seen [B] in/out: bit j set = unknown
+ * row j is remembered (persistent) or was sighted in the agent's last step (not persistent), start at 0; yaw [B], u_att [B]
+ * in/out (io_dtype; u_att starts at NaN; for DynamicUnicycle2D yaw, when given, receives X[2]); traj_yaw [n_steps,B] and
+ * traj_seen [n_steps,B] optional, beside traj_X / traj_U (rows of frozen agents repeat their last values).
+ * Models: DynamicUnicycle2D, SingleIntegrator2D, DoubleIntegrator2D; others return SC_ERR_UNSUPPORTED.
+ */
+int sc_tracking_sense_rollout_batch(const sc_tracking_params* params, const sc_sense_params* sense,
+                                    int64_t B, int32_t M, void* X, const void* waypoints, const int32_t* n_wp,
+                                    int32_t* wp_index, int32_t* state_machine, void* goal, const void* obs_table,
+                                    const void* unknown_table, int64_t* seen, void* yaw, void* u_att, void* u_last,
+                                    int32_t* ret, int32_t* ret_step, void* traj_X, void* traj_U, void* traj_yaw,
+                                    int64_t* traj_seen, void* stream);
 
 /* Closed loop for the arm (SURVEY 8f-1 for Manipulator2D): `n_steps` iterations of LocalTrackingController.control_step
  * (tracking.py:559-668; goal_reached on the end effector :263-268; update_goal :497-535) with nominal_input / step of

@@ -21,6 +21,6 @@ from .position_control.optimal_decay_mpc_cbf import OptimalDecayMPCCBF, BatchedO
 from .position_control.optimal_decay_mpc_cbf_gn import OptimalDecayGnMPCCBF, BatchedOptimalDecayGnMPCCBF  # noqa: F401
 from .shielding import MPS, BatchedShield, Gatekeeper  # noqa: F401
 from .robots.spec import RobotHandle, complete_robot_spec  # noqa: F401
-from .tracking import BatchedTrackingController, BatchedFleetTrackingController  # noqa: F401
+from .tracking import BatchedTrackingController, BatchedFleetTrackingController, BatchedSensingTrackingController  # noqa: F401
 
 __version__ = "0.1.0"

@@ -340,6 +340,19 @@ class TrackingParams(C.Structure):
     ]
 
 
+ATT_NONE, ATT_SIMPLE, ATT_VELOCITY_TRACKING_YAW = 0, 1, 2                                   # SC_ATT_*
+SENSE_MAX_UNKNOWN = 64                                                                       # SC_SENSE_MAX_UNKNOWN
+
+
+class SenseParams(C.Structure):
+    """Mirror of ``sc_sense_params``."""
+    _fields_ = [
+        ("n_unknown", C.c_int32), ("persistent", C.c_int32), ("att_type", C.c_int32), ("reserved", C.c_int32),
+        ("fov_angle", C.c_double), ("cam_range", C.c_double), ("w_max", C.c_double),
+        ("att_kp", C.c_double), ("att_preview_time", C.c_double), ("simple_yaw_rate", C.c_double),
+    ]
+
+
 # every symbol include/safe_control_amd.h declares, with its ctypes signature
 SYMBOLS = {
     "sc_version": (C.c_int, []),
@@ -412,6 +425,8 @@ SYMBOLS = {
     "sc_tracking_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "sc_tracking_fleet_step_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32, C.c_int32]
                                      + [C.c_void_p] * 15),
+    "sc_tracking_sense_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.POINTER(SenseParams), C.c_int64, C.c_int32]
+                                        + [C.c_void_p] * 19),
     "sc_mpccbf_solve_batch_host": (C.c_int, [C.POINTER(MpcCbfParams), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int]),

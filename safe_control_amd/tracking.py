@@ -4,8 +4,11 @@
 ``LocalTrackingController`` (tracking.py:36-756) for the part of ``control_step`` that surrounds the
 solve: goal / state machine, nearest-unpassed obstacle selection, nominal input, CBF-QP, collision
 checks, robot step and return code all run on the GPU, ``n`` control steps per launch, with every
-agent's state resident in registers between steps.  Rendering, sensing footprints, unknown-obstacle
-detection and attitude controllers are out of scope.
+agent's state resident in registers between steps.  ``BatchedSensingTrackingController`` adds what the
+reference's unknown-environment scenario needs: 'fov' detection of unknown obstacles with their memory,
+and the integrators' heading under the 'simple' / 'velocity_tracking_yaw' attitude controllers
+(csrc/tracking_sense.hip).  Rendering and everything built on polygon geometry stay out of scope: 'ray'
+detection, sensing footprints (return code 1), the 'visibility_*' and 'gatekeeper' attitude controllers.
 
 Host side (this file) only prepares waypoints the way ``set_waypoints`` / ``filter_waypoints`` do
 (tracking.py:197-249) and owns the device tensors.  No CPU fallback.
@@ -53,7 +56,8 @@ class BatchedTrackingController:
         if self.model not in _lib.MODEL_IDS or self.model == "Quad2D":
             raise ValueError(f"the batched closed loop does not support model {self.model!r}")
         # the integrators keep their heading outside the state (robots/robot.py:66-72); their rotate state runs the
-        # attitude controllers, which are out of scope: enable_rotation must be off and the heading then never changes
+        # attitude controllers, which this class does not have (BatchedSensingTrackingController does): enable_rotation
+        # must be off and the heading then never changes
         self.integrator = self.model in ("SingleIntegrator2D", "DoubleIntegrator2D")
         if self.integrator and enable_rotation:
             raise ValueError("SingleIntegrator2D / DoubleIntegrator2D run with enable_rotation=False")
@@ -575,6 +579,154 @@ class BatchedQuadTrackingController(BatchedTrackingController):
                 tU[k] = self.u_pos
         self.steps_done += n
         return (self.ret, tX, tU) if record else self.ret
+
+
+class BatchedSensingTrackingController(BatchedTrackingController):
+    """The closed loop with a camera cone and a heading of its own (csrc/tracking_sense.hip): what
+    ``LocalTrackingController.control_step`` does around a CBF-QP in the reference's
+    ``examples/test_unknown_env.py`` scenario.
+
+    * ``unknown_obs`` / ``set_unknown_obs(rows)``: a second obstacle table (at most 64 rows) that an agent cannot see
+      until a row enters its camera cone ('fov' detection, utils/detection.py:28-87).  Sighted rows join the CBF-QP's
+      candidates as circles and, with ``unknown_obs_persistent_fov`` (default), stay in the agent's memory ``seen``
+      (int64 bit mask, bit j = row j); every unknown row counts in the collision tests whether seen or not.
+    * SingleIntegrator2D / DoubleIntegrator2D with ``enable_rotation=True``: ``yaw`` and ``u_att`` (NaN = none) are
+      turned by ``controller_type['att']`` = 'simple' or 'velocity_tracking_yaw' (default), tracking.py:156-181.
+    * DynamicUnicycle2D looks along its own heading ``X[:, 2]``.
+
+    Spec keys, with the reference's defaults: ``fov_angle`` (70 degrees), ``cam_range`` (3.0), ``w_max`` (0.5 for the
+    integrators), ``unknown_obs_persistent_fov`` (True), ``unknown_obs_detection`` ('fov' only), ``simple_yaw_rate``
+    (``w_max``), ``velocity_tracking_yaw_kp`` (1.5), ``velocity_tracking_yaw_preview_time`` (0.0).  Not built, because
+    they need polygon geometry: 'ray' detection, sensing footprints (return code 1), the 'visibility_*' and
+    'gatekeeper' attitude controllers.
+
+    ``control_step(n, record=False)`` returns ``ret`` or ``(ret, traj_X, traj_U, traj_yaw, traj_seen)``.
+    """
+
+    MODELS = ("DynamicUnicycle2D", "SingleIntegrator2D", "DoubleIntegrator2D")
+    ATT_TYPES = {"simple": _lib.ATT_SIMPLE, "velocity_tracking_yaw": _lib.ATT_VELOCITY_TRACKING_YAW}
+    POLYGON_ATT = ("visibility_raycast", "visibility_area", "visibility", "gatekeeper")
+
+    def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, unknown_obs=None,
+                 io_dtype="f64", device="cuda:0"):
+        # every argument is checked here, before the base class creates the first device tensor
+        controller_type = dict(controller_type or {})
+        robot_spec = dict(robot_spec)
+        model = robot_spec.get("model")
+        if model not in self.MODELS:
+            raise ValueError(f"the sensing loop supports {', '.join(self.MODELS)}; not {model!r}")
+        if controller_type.get("pos", "cbf_qp") != "cbf_qp":
+            raise ValueError("the sensing loop's position controller is 'cbf_qp'")
+        integrator = model != "DynamicUnicycle2D"
+        att = controller_type.get("att", "velocity_tracking_yaw")                     # tracking.py:46
+        self.att_type = _lib.ATT_NONE
+        if integrator and enable_rotation:                                            # tracking.py:156-181
+            if att in self.POLYGON_ATT:
+                raise ValueError(f"attitude controller {att!r} needs polygon geometry (sensing footprints), which is not built: "
+                                 "'simple' or 'velocity_tracking_yaw'")
+            if att not in self.ATT_TYPES:
+                raise ValueError(f"unknown attitude controller type {att!r}: 'simple' or 'velocity_tracking_yaw'")
+            self.att_type = self.ATT_TYPES[att]
+        mode = str(robot_spec.get("unknown_obs_detection", "fov")).lower()            # robots/robot.py:800-804
+        if mode == "ray":
+            raise ValueError("unknown_obs_detection 'ray' intersects sensing-footprint polygons, which is not built: 'fov'")
+        if mode != "fov":
+            raise ValueError(f"unsupported unknown_obs_detection mode {mode!r}")
+        if io_dtype not in ("f32", "f64"):
+            raise ValueError("io_dtype must be 'f32' or 'f64'")
+        nc = int(robot_spec.get("num_constraints", 10))
+        if not 1 <= nc <= _lib.TRACKING_MAX_CONSTRAINTS:
+            raise ValueError(f"num_constraints must be in [1, {_lib.TRACKING_MAX_CONSTRAINTS}]")
+        self.cam_range = float(robot_spec.get("cam_range", 3.0))                       # robots/robot.py:57-59
+        self.w_max = float(robot_spec.get("w_max", 0.5))
+        self.persistent = bool(robot_spec.get("unknown_obs_persistent_fov", True))
+        self.simple_yaw_rate = float(robot_spec.get("simple_yaw_rate", self.w_max))    # simple_attitude.py
+        self.att_kp = float(robot_spec.get("velocity_tracking_yaw_kp", 1.5))           # velocity_tracking_yaw.py:31-33
+        self.att_preview_time = float(robot_spec.get("velocity_tracking_yaw_preview_time", 0.0))
+        self.merge_tol = float(robot_spec.get("unknown_obs_merge_tol", 1e-3))          # robots/robot.py:781-782
+        self.merge_radius_tol = float(robot_spec.get("unknown_obs_merge_radius_tol", 1e-2))
+        fov = math.radians(float(robot_spec.get("fov_angle", 70.0)))
+        for name, val in (("fov_angle", fov), ("cam_range", self.cam_range), ("w_max", self.w_max)):
+            if not (math.isfinite(val) and val > 0):
+                raise ValueError(f"{name} must be finite and positive")
+        unknown_rows = self._normalise_unknown(unknown_obs)
+        # the base class refuses a rotating integrator; this class supplies what it lacks, so it is set up as a non-rotating one
+        super().__init__(X0, robot_spec, controller_type={"pos": "cbf_qp"}, dt=dt,
+                         enable_rotation=(enable_rotation and not integrator), obs=obs, dyn_obs=False, io_dtype=io_dtype, device=device)
+        self.enable_rotation = bool(enable_rotation)
+        torch = self.torch
+        yaw0 = self.yaw if self.integrator else self.X[:, 2].double().cpu().numpy()
+        self.yaw = torch.tensor(np.asarray(yaw0, dtype=np.float64), dtype=self.tdtype, device=self.device)
+        self.u_att = torch.full((self.B,), math.nan, dtype=self.tdtype, device=self.device)
+        self.seen = torch.zeros(self.B, dtype=torch.int64, device=self.device)
+        self._set_unknown_rows(unknown_rows)
+
+    def _normalise_unknown(self, rows):
+        """tracking.py:277-291, then what the kernel and the reference's memory can hold (robots/robot.py:773-797)."""
+        u = np.array([] if rows is None else rows, dtype=np.float64)
+        if u.ndim == 1 and u.size > 0:
+            u = u.reshape(1, -1)
+        if u.size == 0:
+            u = np.empty((0, 7))
+        elif u.shape[1] < 7:
+            u = np.hstack((u, np.zeros((u.shape[0], 7 - u.shape[1]))))
+        elif u.shape[1] > 7:
+            u = u[:, :7]
+        if len(u) > _lib.SENSE_MAX_UNKNOWN:
+            raise ValueError(f"at most {_lib.SENSE_MAX_UNKNOWN} unknown obstacles (one bit each of the agents' memory)")
+        seen_r = np.where(u[:, 6] >= 0.5, np.maximum(np.maximum(u[:, 2], u[:, 3]), 0.0), u[:, 2])   # detection.py:65-69
+        flag = np.where(u[:, 6] >= 0.5, 0.0, u[:, 6])
+        for i in range(len(u)):
+            for j in range(i):
+                if (np.linalg.norm(u[i, :2] - u[j, :2]) <= self.merge_tol and abs(seen_r[i] - seen_r[j]) <= self.merge_radius_tol
+                        and abs(flag[i] - flag[j]) <= 0.5):
+                    raise ValueError(f"unknown obstacles {j} and {i} are one obstacle to the reference's memory (centres within "
+                                     f"{self.merge_tol}, radii within {self.merge_radius_tol})")
+        return np.ascontiguousarray(u)
+
+    def _set_unknown_rows(self, u):
+        self.unknown_obs = self.torch.tensor(u, dtype=self.tdtype, device=self.device).contiguous()
+        self.seen.zero_()                                           # reset_unknown_obs_memory (robots/robot.py:755-758)
+
+    def set_unknown_obs(self, rows):
+        self._set_unknown_rows(self._normalise_unknown(rows))
+
+    def set_waypoints(self, waypoints):
+        yaw_t = self.yaw
+        self.yaw = yaw_t.double().cpu().numpy()                     # the base class reads the headings on the host
+        try:
+            super().set_waypoints(waypoints)
+        finally:
+            self.yaw = yaw_t
+
+    def _sense_params(self):
+        s = _lib.SenseParams()
+        s.n_unknown = int(self.unknown_obs.shape[0])
+        s.persistent = 1 if self.persistent else 0
+        s.att_type = self.att_type
+        s.fov_angle, s.cam_range, s.w_max = self.fov_angle, self.cam_range, self.w_max
+        s.att_kp, s.att_preview_time, s.simple_yaw_rate = self.att_kp, self.att_preview_time, self.simple_yaw_rate
+        return s
+
+    def control_step(self, n=1, record=False):
+        """Advance ``n`` control steps in one launch.  Returns ``ret`` [B], or ``(ret, traj_X [n,B,4], traj_U [n,B,2],
+        traj_yaw [n,B], traj_seen [n,B] int64)`` when ``record``."""
+        torch = self.torch
+        if self.waypoints is None:
+            raise RuntimeError("call set_waypoints first")
+        p, s = self._params(n), self._sense_params()
+        mk = lambda shape, dt_=None: torch.empty(shape, dtype=dt_ or self.tdtype, device=self.device) if record else None
+        tX, tU, tYaw, tSeen = mk((n, self.B, 4)), mk((n, self.B, 2)), mk((n, self.B)), mk((n, self.B), torch.int64)
+        ptr = lambda a: a.data_ptr() if a is not None and a.numel() else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sc_tracking_sense_rollout_batch(
+            C.byref(p), C.byref(s), self.B, int(self.obs.shape[0]), self.X.data_ptr(), self.waypoints.data_ptr(),
+            self.n_wp.data_ptr(), self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(),
+            ptr(self.obs), ptr(self.unknown_obs), self.seen.data_ptr(), self.yaw.data_ptr(), self.u_att.data_ptr(),
+            self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), ptr(tX), ptr(tU), ptr(tYaw), ptr(tSeen), stream)
+        _lib.check(rc, "sc_tracking_sense_rollout_batch")
+        self.steps_done += n
+        return (self.ret, tX, tU, tYaw, tSeen) if record else self.ret
 
 
 class BatchedFleetTrackingController(BatchedTrackingController):
