@@ -357,7 +357,10 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TI
 //   * FULL: B is a multiple of the 8 agents of a wave, so there is no `active` guard at all; !FULL keeps it (c.B);
 //   * HAS_H: h_out is non-null;
 //   * the obstacle row arrives with two loads (16 + 12 bytes, f32 storage) instead of seven;
-//   * the f64 sincos reads its sixteen constants, and clip_box its `lo - tol` / `hi + tol`, from the argument block.
+//   * the f64 sincos reads its sixteen constants, and clip_box its `lo - tol` / `hi + tol`, from the argument block;
+//   * what only a rare wave needs -- a flat direction of the box clip, a partner row parallel to a line, a bad obstacle flag -- sits
+//     under one wave-uniform branch each, and the min / max of values that cannot be signalling NaNs skip the canonicalising
+//     v_max(x, x) (sc_group.hpp, "cold paths of the specialised solve"; tests/test_cbfqp_coldpaths_gpu.py runs the cold blocks).
 // Arithmetic and its order are those of the generic kernel, so both return the same bits (tests/test_cbfqp_special_gpu.py).
 // Six pointers in order of first use are preloaded (12 dwords); n_obs, B, K and obs_shared are not arguments.
 // The constants travel as four 64-byte vectors so that a wave fetches them with four scalar loads (field by field the compiler
@@ -421,7 +424,7 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
     Agent<TC> ag;                                          // make_agent with the constants of its sincos from the argument block
     ag.x = TC(xs.v[0]); ag.y = TC(xs.v[1]); ag.th = TC(xs.v[2]); ag.v = TC(xs.v[3]);
-    sincos_tab(ag.th, sc, &ag.s, &ag.c);
+    sincos_tab_sfma(ag.th, sc, &ag.s, &ag.c);
     ag.f0 = ag.v * ag.c;
     ag.f1 = ag.v * ag.s;
 
@@ -439,18 +442,23 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     normalise_row_as_generic(a0, a1, cc, poison);
 
     // ---- the solve, the slack check and the outputs: as in cbfqp_coop_kernel ------------------
+    // The *_raw forms (sc_group.hpp) are qp_begin / qp_finish_box / qp_row_margin without the canonicalising v_max(x, x): the box
+    // bounds arrive quieted (launch_coop8_du), everything else here is converted from storage or the result of arithmetic.
     QpState<TC> S;
-    qp_begin(S, ur0, ur1, k);
+    qp_begin_raw(S, ur0, ur1, k);
     coop_solve_all8_full<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, bt);
-    qp_finish_box(S, k);
-    TC worst = qp_row_margin(num<TC>::inf(), a0, a1, cc, S.u0, S.u1, poison);
+    qp_finish_box_raw(S, k);
+    TC worst = qp_row_margin_raw(a0, a1, cc, S.u0, S.u1, poison);
     const bool nan_mine = !(poison == poison);
     worst = nan_mine ? -num<TC>::inf() : worst;
     worst = min8_raw(worst);
-    const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
-    const bool bad_any = ((bad_mask >> (lane & ~7u)) & 0xffull) != 0ull;
     int st = qp_status(S, worst, TC(0), k);
-    if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
+    if (__builtin_amdgcn_ballot_w64(bad_mine) != 0ull) {   // wave-uniform, cold: the group's byte of the ballot, as in cbfqp_coop_kernel
+        asm volatile("");                                  // keeps the block a branch: flattened, its shift and byte test run in every wave
+        const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
+        const bool bad_any = ((bad_mask >> (lane & ~7u)) & 0xffull) != 0ull;
+        if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
+    }
     TC u0 = S.u0, u1 = S.u1;
     if (st != SC_STATUS_OPTIMAL) { u0 = num<TC>::nan(); u1 = num<TC>::nan(); }
     if (active && sub == 0) {
@@ -479,6 +487,18 @@ static inline bool sc_cbfqp_generic() {
     return v;
 }
 
+// x with a signalling NaN made quiet, every other value as it is (the sign of a zero included): what v_max(x, x) does to a kernel
+// argument, done once on the host so that the kernel's raw min / max may take the box bounds as they come
+static inline double sc_quieted(double x) {
+    if (x != x) {
+        unsigned long long b;
+        __builtin_memcpy(&b, &x, sizeof(b));
+        b |= 0x0008000000000000ull;
+        __builtin_memcpy(&x, &b, sizeof(b));
+    }
+    return x;
+}
+
 template <typename TIO>
 static hipError_t launch_coop8_du(const sc_cbfqp_params& p, long long B, const void* X, const void* u_ref, const void* obs,
                                   void* u_out, int* status, void* h_out, hipStream_t stream) {
@@ -488,8 +508,8 @@ static hipError_t launch_coop8_du(const sc_cbfqp_params& p, long long B, const v
     Coop8Consts c;
     c.t0 = sc_d8{t.two_over_pi, t.pio2_1, t.pio2_2, t.pio2_3, t.s[0], t.s[1], t.s[2], t.s[3]};
     c.t1 = sc_d8{t.s[4], t.s[5], t.c[0], t.c[1], t.c[2], t.c[3], t.c[4], t.c[5]};
-    c.k0 = sc_d8{k.R, k.g1, k.g2, k.inv_dt, k.inv_dt2, k.lo0, k.hi0, k.lo1};
-    c.k1 = sc_d8{k.hi1, bt.lo0, bt.hi0, bt.lo1, bt.hi1, 0.0, 0.0, 0.0};
+    c.k0 = sc_d8{k.R, k.g1, k.g2, k.inv_dt, k.inv_dt2, sc_quieted(k.lo0), sc_quieted(k.hi0), sc_quieted(k.lo1)};
+    c.k1 = sc_d8{sc_quieted(k.hi1), bt.lo0, bt.hi0, bt.lo1, bt.hi1, 0.0, 0.0, 0.0};
     c.hard = k.hard;
     c.B = (unsigned)B;
     const dim3 grid(coop_grid((unsigned)((B + 7) / 8))), block(64);

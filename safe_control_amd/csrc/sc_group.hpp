@@ -283,7 +283,121 @@ __device__ __forceinline__ void clip_box_tol(LineQP<T>& L, const CbfConsts<T>& k
         L.lo = fmax_(L.lo, lo); L.hi = fmin_(L.hi, hi);
     }
 }
-// coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`) and the box bounds above
+// ---- cold paths of the specialised solve -----------------------------------------------------------------------------------
+// What follows serves cbfqp_coop8_du_kernel only.  A lone wave pays for every instruction it executes, and three groups of them
+// decide something that an ordinary wave never needs: a flat direction of the box clip, a partner row parallel to the lane's line,
+// and the canonicalising v_max(x, x) in front of a min / max.  Each rare case moves under ONE wave-uniform branch whose block
+// recomputes the affected values with the operations of the forms above, so every value that can reach an output keeps its bits.
+// How many of the 512 waves of the benchmark batch take each branch is counted in DESIGN.md 1b (none does).
+
+// min / max forms whose operands the compiler would canonicalise first (asm outputs, kernel arguments): the argument above
+// min_raw holds for each of them -- see the call sites.  `b` of the *_s forms is wave-uniform (a kernel argument, an SGPR pair).
+__device__ __forceinline__ double max_raw_s(double a, double b) { double r; asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
+__device__ __forceinline__ double min_raw_s(double a, double b) { double r; asm("v_min_f64 %0, %1, %2" : "=v"(r) : "v"(a), "s"(b)); return r; }
+__device__ __forceinline__ double max_zero_raw(double a) { double r; asm("v_max_f64 %0, %1, 0" : "=v"(r) : "v"(a)); return r; }             // max(a, 0)
+__device__ __forceinline__ double max_one_raw(double a) { double r; asm("v_max_f64 %0, %1, 1.0" : "=v"(r) : "v"(a)); return r; }            // max(a, 1)
+__device__ __forceinline__ double max_abs_abs_raw(double a, double b) { double r; asm("v_max_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+
+// qp_begin / qp_finish_box (sc_qp2.hpp) without the four v_max(x, x) on the box bounds and the two on the point.  The bounds are
+// kernel arguments, which the compiler must assume could be signalling NaNs: launch_coop8_du hands them over quieted, u_ref is
+// converted from storage, and the point is the output of a min / max or of arithmetic.  Operand order as the compiler emits it
+// for fmin_(fmax_(u, lo), hi).
+__device__ __forceinline__ void qp_begin_raw(QpState<double>& S, double ur0, double ur1, const CbfConsts<double>& k) {
+    S.ur0 = ur0; S.ur1 = ur1;
+    S.u0 = min_raw_s(max_raw_s(ur0, k.lo0), k.hi0);
+    S.u1 = min_raw_s(max_raw_s(ur1, k.lo1), k.hi1);
+}
+__device__ __forceinline__ void qp_finish_box_raw(QpState<double>& S, const CbfConsts<double>& k) {
+    S.u0 = min_raw_s(max_raw_s(S.u0, k.lo0), k.hi0);
+    S.u1 = min_raw_s(max_raw_s(S.u1, k.lo1), k.hi1);
+}
+// qp_row_margin (sc_qp2.hpp) of one row against worst = +inf, with max(1, |ci|) as one instruction: ci is the product of
+// arithmetic (normalise_row), never a signalling NaN.
+__device__ __forceinline__ double qp_row_margin_raw(double a0, double a1, double ci, double u0, double u1, double& poison) {
+    const double s = a0 * u0 + (a1 * u1 + ci);
+    const double m = s + num<double>::tol_feas() * max_abs_one_raw(ci);
+    poison += 0.0 * s;
+    return fmin_(num<double>::inf(), m);
+}
+
+// clip_box_tol with the flat directions (d == 0: the selects, the four `inside` compares, the +-inf literals) under one branch.
+// A lane without a flat direction gets fmin_(t1, t2) / fmax_(t1, t2) from both forms; a wave in which some lane has one runs
+// clip_box_tol itself over the whole wave, which overwrites lo / hi with exactly what it gives today.  The ballot is taken over
+// every lane, not only the violated ones: masking it with a flag from another basic block costs two more vector instructions.
+template <typename T>
+__device__ __forceinline__ void clip_box_tol_lazy(LineQP<T>& L, const CbfConsts<T>& k, const BoxTol<T>& bt) {
+    const T r0 = rcp_(L.d0), r1 = rcp_(L.d1);
+    const T t1 = (k.lo0 - L.p0) * r0, t2 = (k.hi0 - L.p0) * r0;
+    const T t3 = (k.lo1 - L.p1) * r1, t4 = (k.hi1 - L.p1) * r1;
+    const bool flat = (L.d0 == T(0)) || (L.d1 == T(0));
+    L.lo = fmax_(fmin_(t1, t2), fmin_(t3, t4));
+    L.hi = fmin_(fmax_(t1, t2), fmax_(t3, t4));
+    if (__builtin_amdgcn_ballot_w64(flat) != 0ull) clip_box_tol(L, k, bt);             // wave-uniform, cold
+}
+
+// clip_row_coop with the parallel-row test made lazy: `dead` needs par_viol only where the partner is parallel to the line
+// (!pos && !neg), so the loop keeps "some partner was parallel" and the caller takes one wave-uniform branch on its ballot
+// (partners8_dead below).  The restriction of the interval is clip_row_coop's, operation for operation.
+template <typename T>
+__device__ __forceinline__ void clip_row_coop_lazy(LineQP<T>& L, bool& anypar, T g0, T g1, T gc) {
+    const T a = g0 * L.d0 + g1 * L.d1;
+    const T r = g0 * L.p0 + (g1 * L.p1 + gc);
+    const bool pos = a > num<T>::eps_par();
+    const bool neg = !(a >= -num<T>::eps_par());
+    const T q = r * rcp_(fabs_(a));
+    anypar |= !pos && !neg;
+    L.lo = max_neg_raw(L.lo, keep_or_nan(pos, q));
+    L.hi = min_raw(L.hi, keep_or_nan(neg, q));
+}
+template <typename TC, int... Xs>
+__device__ __forceinline__ void clip_partners8_lazy(LineQP<TC>& L, bool& anypar, TC a0, TC a1, TC cc, std::integer_sequence<int, Xs...>) {
+    const TC m0 = dpp_mov<0x141>(a0), m1 = dpp_mov<0x141>(a1), mc = dpp_mov<0x141>(cc);
+    (clip_row_coop_lazy(L, anypar, group_xor8<TC, Xs + 1>(a0, m0), group_xor8<TC, Xs + 1>(a1, m1), group_xor8<TC, Xs + 1>(cc, mc)), ...);
+}
+// the cold block: `dead` of clip_row_coop for one partner / for the seven, from the line as clip_box left it (p and d do not
+// change in the clips) -- the same a, r and par_viol, so the same flag.  The partners come by shuffles in a loop that stays
+// rolled: the block is cold, and unrolled over DPP moves it is scheduled for overlap and sets the kernel's register count (75).
+template <typename T>
+__device__ __forceinline__ bool row_dead_coop(const LineQP<T>& L, T g0, T g1, T gc) {
+    const T a = g0 * L.d0 + g1 * L.d1;
+    const T r = g0 * L.p0 + (g1 * L.p1 + gc);
+    const bool pos = a > num<T>::eps_par();
+    const bool neg = !(a >= -num<T>::eps_par());
+    const bool par_viol = r < -num<T>::tol_feas() * max_abs_one_raw(gc);
+    return !pos && !neg && par_viol;
+}
+template <typename TC>
+__device__ __forceinline__ bool partners8_dead(const LineQP<TC>& L, TC a0, TC a1, TC cc) {
+    bool dead = false;
+#pragma nounroll
+    for (int x = 1; x < 8; ++x) dead |= row_dead_coop(L, __shfl_xor(a0, x, 8), __shfl_xor(a1, x, 8), __shfl_xor(cc, x, 8));
+    return dead;
+}
+
+// coop_pick_winner for 8 lanes per agent without the v_max(x, x) in front of lo, hi, |lo| and |hi|: the interval ends come out of
+// the raw min / max of the clips (inline assembly, so the compiler cannot see that they are canonical); those return one of their
+// operands or a quieted NaN, and their operands are products of arithmetic.  Operand order as the compiler emits it for the
+// expressions of coop_pick_winner: max(lo, 0), then min(., hi); max(|lo|, |hi|), then max(., 1).
+__device__ __forceinline__ void coop_pick_winner8_raw(QpState<double>& S, const LineQP<double>& L, bool ok, int sub, int lane) {
+    using TC = double;
+    const TC inf = num<TC>::inf();
+    TC t = min_raw(max_zero_raw(L.lo), L.hi);
+    const bool inverted = L.lo > L.hi;
+    t = inverted ? TC(0.5) * (L.lo + L.hi) : t;
+    const bool empty = L.lo > L.hi + num<TC>::tol_feas() * max_one_raw(max_abs_abs_raw(L.lo, L.hi));
+    const TC v0 = L.p0 + t * L.d0, v1 = L.p1 + t * L.d1;
+    const TC e0 = v0 - S.ur0, e1 = v1 - S.ur1;
+    TC cost = e0 * e0 + e1 * e1;
+    cost = (ok && !empty && (cost == cost)) ? cost : inf;
+    const TC best = min8_raw(cost);
+    bool has;
+    const bool mine = group_first<8>(__builtin_amdgcn_ballot_w64((cost == best) && (best < inf)), lane, sub, has);
+    const TC s0 = group_pick<8>(mine, v0), s1 = group_pick<8>(mine, v1);
+    S.u0 = has ? s0 : S.u0;
+    S.u1 = has ? s1 : S.u1;
+}
+
+// coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`), the box bounds above and the cold paths out of the way
 template <typename TC>
 __device__ __forceinline__ void coop_solve_all8_full(QpState<TC>& S, int sub, int lane, TC a0, TC a1, TC cc,
                                                      const CbfConsts<TC>& k, const BoxTol<TC>& bt) {
@@ -291,10 +405,13 @@ __device__ __forceinline__ void coop_solve_all8_full(QpState<TC>& S, int sub, in
     LineQP<TC> L;
     const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;
     if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;
-    clip_box_tol(L, k, bt);
+    clip_box_tol_lazy(L, k, bt);
+    bool anypar = false;
+    clip_partners8_lazy(L, anypar, a0, a1, cc, std::make_integer_sequence<int, 7>{});
     bool dead = false;
-    clip_partners8(L, dead, a0, a1, cc, std::make_integer_sequence<int, 7>{});
-    coop_pick_winner<TC, 8>(S, L, viol && !dead, sub, lane);
+    if (__builtin_amdgcn_ballot_w64(anypar) != 0ull)                         // wave-uniform, cold: some row of the wave parallel to some line
+        dead = partners8_dead(L, a0, a1, cc);
+    coop_pick_winner8_raw(S, L, viol && !dead, sub, lane);
 }
 
 // The same for 16 lanes per agent (K <= 16; one DPP row per agent): fifteen partners by row_ror, reductions by quad permutes and

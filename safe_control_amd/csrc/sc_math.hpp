@@ -94,6 +94,40 @@ __device__ __forceinline__ void sincos_tab(double x, const SinCosTab& t, double*
     *s = (n & 2) ? -sv : sv;
     *c = ((n + 1) & 2) ? -cv : cv;
 }
+// sincos_tab with every Horner step after the first written as the three-address v_fma_f64 d, z, p, s[c:c+1].  Left to itself the
+// compiler picks the two-address v_fmac_f64 for those steps, whose accumulator must be a VGPR: it copies each constant out of the
+// argument block's SGPRs with a pair of v_mov_b32 first, twenty moves on the short path.  The constant is the addend and the only
+// scalar operand of the instruction, which gfx9 allows.  The first step of each polynomial names two constants and stays with
+// the compiler (one of them goes through a VGPR).  Same operations on the same values in the same order as sincos_tab and sincos_.
+__device__ __forceinline__ double fma_sconst(double a, double b, double c) {        // fma(a, b, c), c wave-uniform
+    double d;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
+    return d;
+}
+__device__ __forceinline__ void sincos_tab_sfma(double x, const SinCosTab& t, double* s, double* c) {
+    if (!(fabs(x) < 1.0e5)) { sincos(x, s, c); return; }
+    const double k = rint(x * t.two_over_pi);
+    double r = __builtin_fma(-k, t.pio2_1, x);
+    r = __builtin_fma(-k, t.pio2_2, r);
+    r = __builtin_fma(-k, t.pio2_3, r);
+    const double z = r * r;
+    double ps = __builtin_fma(z, t.s[0], t.s[1]);
+    ps = fma_sconst(z, ps, t.s[2]);
+    ps = fma_sconst(z, ps, t.s[3]);
+    ps = fma_sconst(z, ps, t.s[4]);
+    const double ks = __builtin_fma(z * r, fma_sconst(z, ps, t.s[5]), r);
+    double pc = __builtin_fma(z, t.c[0], t.c[1]);
+    pc = fma_sconst(z, pc, t.c[2]);
+    pc = fma_sconst(z, pc, t.c[3]);
+    pc = fma_sconst(z, pc, t.c[4]);
+    pc = fma_sconst(z, pc, t.c[5]);
+    const double hz = 0.5 * z, w = 1.0 - hz;
+    const double kc = w + (((1.0 - w) - hz) + z * (z * pc));
+    const int n = (int)k & 3;
+    const double sv = (n & 1) ? kc : ks, cv = (n & 1) ? ks : kc;
+    *s = (n & 2) ? -sv : sv;
+    *c = ((n + 1) & 2) ? -cv : cv;
+}
 __device__ __forceinline__ float sqrt_(float x) { return sqrtf(x); }
 __device__ __forceinline__ double sqrt_(double x) { return sqrt(x); }
 __device__ __forceinline__ float fabs_(float x) { return fabsf(x); }
