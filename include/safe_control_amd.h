@@ -731,12 +731,41 @@ typedef struct sc_tracking_params {
  * whose ret != 0 is frozen); ret_step [B] in/out: step_offset + step index inside the launch at which
  * ret turned non-zero (initialise to -1; untouched for agents that were already frozen); traj_X [n_steps,B,4], traj_U [n_steps,B,2] optional (NULL to skip):
  * state AFTER each step and the input applied (rows of frozen agents repeat their last state).
+ * The same loop with the optimal-decay CBF-QP as its position controller: sc_tracking_od_rollout_batch below.
  */
 int sc_tracking_rollout_batch(const sc_tracking_params* params, int64_t B, int32_t M,
                               void* X, const void* waypoints, const int32_t* n_wp,
                               int32_t* wp_index, int32_t* state_machine, void* goal,
                               void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
                               void* traj_X, void* traj_U, void* stream);
+
+/* The fused loop with position controller 'optimal_decay_cbf_qp' (tracking.py:148-150, dynamic_env/main.py:167-179; kernel
+ * csrc/tracking_od.hip).  It differs from sc_tracking_rollout_batch in four places:
+ *   gains        'track' calls nominal_input(goal, k_omega=3.0, k_a=0.5, k_v=0.5) (tracking.py:601-602): track.k_omega / k_a / k_v carry
+ *                those; stop() keeps its own gain k_a_stop (dynamic_unicycle2D.py:106-108) and rotate_to its 2.0
+ *   one obstacle the controller sees the nearest unpassed obstacle only (row 0 of get_nearest_unpassed_obs); track.num_constraints is
+ *                ignored
+ *   no obstacle  M == 0: the QP is still solved, with A = b = h = h_dot = 0 (optimal_decay_cbf_qp.py:133-137), so the input box applies
+ *   every state  the QP is solved in 'track', 'stop' and 'rotate' alike
+ * Models: DynamicUnicycle2D (circle and superellipsoid rows), KinematicBicycle2D, KinematicBicycle2D_C3BF, KinematicBicycle2D_DPCBF.
+ * Arithmetic is f64; storage follows track.qp.io_dtype.
+ */
+typedef struct sc_tracking_od_params {
+    sc_tracking_params track;   /* track.qp.alpha1/alpha2 (or alpha) carry the optimal-decay gains; k_omega/k_a/k_v are the 'track' gains; num_constraints ignored */
+    double omega_ref[2], p_sb[2];
+    double k_a_stop;            /* stop(): robot_spec['nominal_k_a'] or 1.0 */
+    double reserved;            /* keep 0 */
+} sc_tracking_od_params;
+
+/* X .. traj_U as sc_tracking_rollout_batch.  omega [B,2] in/out: the decay multipliers of the agent's last solve (omega2 = omega_ref[1]
+ * for the rel-degree-1 models); min_h [B] in/out (initialise to +inf): running minimum, over the steps the agent took with an obstacle
+ * present, of the selected obstacle's h; traj_omega [n_steps,B,2] or NULL.  Frozen agents repeat their last values in the traj_* rows.
+ * Every argument is checked before the first HIP call; B == 0 returns SC_OK. */
+int sc_tracking_od_rollout_batch(const sc_tracking_od_params* params, int64_t B, int32_t M,
+                                 void* X, const void* waypoints, const int32_t* n_wp,
+                                 int32_t* wp_index, int32_t* state_machine, void* goal,
+                                 void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
+                                 void* traj_X, void* traj_U, void* omega, void* min_h, void* traj_omega, void* stream);
 
 /* control_step split around the solve, for position controllers that are their own launch (MPC-CBF, optimal-decay
  * MPC-CBF; the reference's default `--algo mpc_cbf`, examples/test_tracking.py:15):

@@ -340,6 +340,12 @@ class TrackingParams(C.Structure):
     ]
 
 
+class TrackingOdParams(C.Structure):
+    """Mirror of ``sc_tracking_od_params``."""
+    _fields_ = [("track", TrackingParams), ("omega_ref", C.c_double * 2), ("p_sb", C.c_double * 2),
+                ("k_a_stop", C.c_double), ("reserved", C.c_double)]
+
+
 ATT_NONE, ATT_SIMPLE, ATT_VELOCITY_TRACKING_YAW = 0, 1, 2                                   # SC_ATT_*
 SENSE_MAX_UNKNOWN = 64                                                                       # SC_SENSE_MAX_UNKNOWN
 
@@ -421,6 +427,7 @@ SYMBOLS = {
     "sc_drift_shield_step_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64] + [C.c_void_p] * 13),
     "sc_drift_shield_rollout_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "sc_tracking_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
+    "sc_tracking_od_rollout_batch": (C.c_int, [C.POINTER(TrackingOdParams), C.c_int64, C.c_int32] + [C.c_void_p] * 16),
     "sc_tracking_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "sc_tracking_fleet_step_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32, C.c_int32]

@@ -39,6 +39,9 @@ hipError_t tracking_apply_launch(const sc_tracking_params& p, long long B, int M
 hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                            int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                            void* tX, void* tU, hipStream_t stream);
+hipError_t tracking_od_launch(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
+                              int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
+                              void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream);
 hipError_t tracking_fleet_launch(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
                                  const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, void* table,
                                  const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream);
@@ -1397,6 +1400,36 @@ int sc_tracking_rollout_batch(const sc_tracking_params* params, int64_t B, int32
     hipError_t e = sc::tracking_launch(*params, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal,
                                        obs_table, u_last, ret, ret_step, traj_X, traj_U, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "tracking kernel launch");
+    return SC_OK;
+}
+
+int sc_tracking_od_rollout_batch(const sc_tracking_od_params* params, int64_t B, int32_t M, void* X, const void* waypoints,
+                                 const int32_t* n_wp, int32_t* wp_index, int32_t* state_machine, void* goal, void* obs_table,
+                                 void* u_last, int32_t* ret, int32_t* ret_step, void* traj_X, void* traj_U, void* omega,
+                                 void* min_h, void* traj_omega, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    const sc_tracking_params* t = &params->track;
+    const sc_cbfqp_params* q = &t->qp;
+    if (B < 0 || M < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0 or M < 0");
+    if (q->model_id < SC_MODEL_DYNAMIC_UNICYCLE2D || q->model_id > SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF)
+        return sc::fail(SC_ERR_UNSUPPORTED, "the optimal-decay rollout is built for DynamicUnicycle2D and the KinematicBicycle2D family");
+    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (t->n_steps < 0 || t->max_waypoints < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_steps < 0 or max_waypoints < 1");
+    if (!(q->dt > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0");
+    if (!(params->p_sb[0] > 0) || !(params->p_sb[1] > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "p_sb must be > 0");
+    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && (!(q->rear_ax_dist > 0) || !(t->wheel_base > 0)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "rear_ax_dist and wheel_base must be > 0 for the KinematicBicycle2D family");
+    if ((size_t)M * 7 * 8 > 160 * 1024) return sc::fail(SC_ERR_UNSUPPORTED, "obstacle table does not fit the LDS");
+    if (B > 0 && (!X || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !u_last || !ret || !ret_step || !omega || !min_h ||
+                  (M > 0 && !obs_table)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B == 0 || t->n_steps == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_od_launch(*params, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal, obs_table,
+                                          u_last, ret, ret_step, traj_X, traj_U, omega, min_h, traj_omega, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "optimal-decay tracking kernel launch");
     return SC_OK;
 }
 

@@ -1,21 +1,15 @@
 // Optimal-decay CBF-QP, one problem per lane.
 //   OptimalDecayCBFQP.solve_control_problem   position_control/optimal_decay_cbf_qp.py:131-158
-// The QP has 4 variables (u0, u1, omega1, omega2), a diagonal Hessian diag(1, 1, p1, p2), ONE general
-// row  a0 u0 + a1 u1 + e1 w1 + e2 w2 + b >= 0  and a box on (u0, u1).  Strictly convex => unique
-// minimiser; it is found exactly by checking the KKT conditions of the 1 + 9 possible active sets
-// (row inactive; row active with each of u0, u1 free / at its lower / at its upper bound).
+// The row build and the 1 + 9 active-set solve live in od_qp.hpp, which the fused closed loop (tracking_od.hip) shares.
 #include <hip/hip_runtime.h>
 
-#include "sc_models.hpp"
+#include "od_qp.hpp"
 
 namespace sc {
 
 template <typename TIO> struct odv2;
 template <> struct odv2<float> { using type = float2; };
 template <> struct odv2<double> { using type = double2; };
-
-template <typename T>
-struct OdSol { T u0, u1, w1, w2, cost; bool ok; };
 
 template <typename TIO, typename TC, int MODEL>
 __global__ __launch_bounds__(256) void odcbfqp_kernel(const sc_odcbfqp_params p, const long long B,
@@ -40,107 +34,22 @@ __global__ __launch_bounds__(256) void odcbfqp_kernel(const sc_odcbfqp_params p,
     const TC r0 = TC(ur.x), r1 = TC(ur.y);
     const TC wr1 = TC(p.omega_ref[0]), wr2 = TC(p.omega_ref[1]);
     const TC p1 = TC(p.p_sb[0]), p2 = TC(p.p_sb[1]);
-    constexpr bool REL2 = (MODEL == SC_MODEL_DYNAMIC_UNICYCLE2D || MODEL == SC_MODEL_KINEMATIC_BICYCLE2D || MODEL == SC_MODEL_QUAD2D);
+    constexpr bool REL2 = od_rel2<MODEL>::value;
 
     // ---- the row: A = dh g, b = dh f (optimal_decay_cbf_qp.py:138-146), e1, e2 -------------------
-    TC a0 = 0, a1 = 0, b = 0, e1 = 0, e2 = 0, h = 0;
-    bool bad = false;
+    OdRow<TC> row = od_row_none<TC>();
     const bool present = has_obs ? (has_obs[agent] != 0) : true;
     if (present) {
         TC o[7];
 #pragma unroll
         for (int f = 0; f < 7; ++f) o[f] = TC(obs[agent * 7 + f]);
-        if constexpr (MODEL == SC_MODEL_QUAD2D) {
-            // optimal_decay_cbf_qp.py:38-45,105-115,141-146 over robots/quad2D.py:166-177 (circle, no flag test) and g of :68-81: both
-            // thrusts enter alike, A = dh_dot_dx g = [a, a], a = 2 (-ex sin th + ez cos th) / m; b = dh_dot_dx f = 2 |v|^2 - 2 g ez
-            const TC ex = ag.x - o[0], ez = ag.y - o[1];
-            const TC dmin = o[2] + k.R;
-            h = (ex * ex + ez * ez) - TC(1.01) * dmin * dmin;
-            const TC hdot = TC(2) * (ex * ag.f0 + ez * ag.f1);
-            a0 = (TC(2) * ex * (-ag.s) + TC(2) * ez * ag.c) * k.inv_mass;
-            a1 = a0;
-            b = TC(2) * ag.f0 * ag.f0 + TC(2) * ag.f1 * ag.f1 + TC(2) * ez * TC(-9.81);
-            e1 = k.g1 * hdot;
-            e2 = k.g2 * h;
-        } else if constexpr (REL2) {
-            TC hdot, d[4];
-            if constexpr (MODEL == SC_MODEL_DYNAMIC_UNICYCLE2D) {
-                if (o[6] == TC(0)) hocbf_circle(ag, o, k.R, TC(1.01), h, hdot, d);
-                else if (o[6] == TC(1)) hocbf_superellipsoid(ag, o, k.R, h, hdot, d);
-                else { bad = true; h = hdot = 0; d[0] = d[1] = d[2] = d[3] = 0; }
-                a0 = d[3]; a1 = d[2];
-            } else {
-                hocbf_circle(ag, o, k.R, TC(1.1), h, hdot, d);
-                a0 = d[3];
-                a1 = -ag.f1 * d[0] + ag.f0 * d[1] + ag.v * k.inv_Lr * d[2];
-            }
-            b = d[0] * ag.f0 + d[1] * ag.f1;
-            e1 = k.g1 * hdot;                    // (alpha1 + alpha2) h_dot
-            e2 = k.g2 * h;                       // alpha1 alpha2 h
-        } else {
-            TC d[4];
-            if constexpr (MODEL == SC_MODEL_KINEMATIC_BICYCLE2D_C3BF) c3bf(ag, o, k.R, h, d);
-            else dpcbf(ag, o, k.R, h, d);
-            a0 = d[3];
-            a1 = -ag.f1 * d[0] + ag.f0 * d[1] + ag.v * k.inv_Lr * d[2];
-            b = d[0] * ag.f0 + d[1] * ag.f1;
-            e1 = k.a1 * h;                       // alpha h
-            e2 = TC(0);
-        }
+        row = od_build_row<TC, MODEL>(ag, o, k);
     }
+    const TC h = row.h;
 
-    // ---- exact solve by KKT enumeration --------------------------------------------------------------
-    const TC tol = num<TC>::tol_feas();
-    const TC c0 = fmin_(fmax_(r0, k.lo0), k.hi0), c1 = fmin_(fmax_(r1, k.lo1), k.hi1);
-    OdSol<TC> best;
-    best.ok = false; best.cost = num<TC>::inf(); best.u0 = c0; best.u1 = c1; best.w1 = wr1; best.w2 = wr2;
-    const TC rowscale = fmax_(TC(1), fabs_(a0 * c0) + fabs_(a1 * c1) + fabs_(e1 * wr1) + fabs_(e2 * wr2) + fabs_(b));
-    // (1) row inactive
-    {
-        const TC s = a0 * c0 + a1 * c1 + e1 * wr1 + e2 * wr2 + b;
-        if (s >= -tol * rowscale) {
-            best.ok = true;
-            best.cost = (c0 - r0) * (c0 - r0) + (c1 - r1) * (c1 - r1);
-        }
-    }
-    // (2) row active, u0 / u1 each free (0), at lo (1) or at hi (2)
-    const TC iw1 = e1 * e1 / p1, iw2 = REL2 ? e2 * e2 / p2 : TC(0);
-#pragma unroll
-    for (int q0 = 0; q0 < 3; ++q0) {
-#pragma unroll
-        for (int q1 = 0; q1 < 3; ++q1) {
-            const TC f0 = q0 == 1 ? k.lo0 : k.hi0, f1 = q1 == 1 ? k.lo1 : k.hi1;
-            const TC x0 = q0 == 0 ? r0 : f0, x1 = q1 == 0 ? r1 : f1;            // fixed at bound, else reference
-            const TC s = a0 * x0 + a1 * x1 + e1 * wr1 + e2 * wr2 + b;             // row value at that point
-            const TC den = (q0 == 0 ? a0 * a0 : TC(0)) + (q1 == 0 ? a1 * a1 : TC(0)) + iw1 + iw2;
-            // stationarity: 2 D (x - r) = lam a on the free variables, row = 0  =>  lam = -2 s / den
-            const TC lam = TC(-2) * s / den;
-            const TC u0 = q0 == 0 ? r0 + TC(0.5) * lam * a0 : f0;
-            const TC u1 = q1 == 0 ? r1 + TC(0.5) * lam * a1 : f1;
-            const TC w1 = wr1 + TC(0.5) * lam * e1 / p1;
-            const TC w2 = REL2 ? wr2 + TC(0.5) * lam * e2 / p2 : wr2;
-            bool ok = (den > TC(0)) && (lam >= -tol);
-            const TC btol = tol * fmax_(TC(1), fmax_(fabs_(k.hi0), fabs_(k.hi1)));
-            // free inputs inside the box, fixed inputs pushed against their bound (multiplier >= 0)
-            if (q0 == 0) ok = ok && (u0 >= k.lo0 - btol) && (u0 <= k.hi0 + btol);
-            if (q0 == 1) ok = ok && (TC(2) * (k.lo0 - r0) - lam * a0 >= -tol);
-            if (q0 == 2) ok = ok && (lam * a0 - TC(2) * (k.hi0 - r0) >= -tol);
-            if (q1 == 0) ok = ok && (u1 >= k.lo1 - btol) && (u1 <= k.hi1 + btol);
-            if (q1 == 1) ok = ok && (TC(2) * (k.lo1 - r1) - lam * a1 >= -tol);
-            if (q1 == 2) ok = ok && (lam * a1 - TC(2) * (k.hi1 - r1) >= -tol);
-            const TC cost = (u0 - r0) * (u0 - r0) + (u1 - r1) * (u1 - r1) + p1 * (w1 - wr1) * (w1 - wr1) +
-                            (REL2 ? p2 * (w2 - wr2) * (w2 - wr2) : TC(0));
-            if (ok && cost < best.cost) {
-                best.ok = true; best.cost = cost; best.u0 = u0; best.u1 = u1; best.w1 = w1; best.w2 = w2;
-            }
-        }
-    }
-    const bool finite = finite_(a0 + a1 + b + e1 + e2 + r0 + r1);
-    int st = (best.ok && finite) ? SC_STATUS_OPTIMAL : SC_STATUS_INFEASIBLE;
-    if (bad) st = SC_STATUS_BAD_OBSTACLE;
-    TC u0 = fmin_(fmax_(best.u0, k.lo0), k.hi0), u1 = fmin_(fmax_(best.u1, k.lo1), k.hi1);
-    TC w1 = best.w1, w2 = best.w2;
-    if (st != SC_STATUS_OPTIMAL) { u0 = u1 = w1 = w2 = num<TC>::nan(); }
+    // ---- exact solve by KKT enumeration (od_qp.hpp) --------------------------------------------------
+    TC u0, u1, w1, w2;
+    const int st = od_solve<TC, REL2>(row, r0, r1, wr1, wr2, p1, p2, k, u0, u1, w1, w2);
     V2 uo; uo.x = TIO(u0); uo.y = TIO(u1);
     reinterpret_cast<V2*>(u_out)[agent] = uo;
     V2 wo; wo.x = TIO(w1); wo.y = TIO(w2);

@@ -644,6 +644,14 @@ __global__ void advance_obstacle_table_kernel(TIO* __restrict__ obs_table, const
     obs_table[7 * m] = TIO(x); obs_table[7 * m + 1] = TIO(y);
 }
 
+// (also the follow-up of the optimal-decay rollout, csrc/tracking_od.hip)
+hipError_t advance_obstacle_table_launch(bool f32, void* table, int M, int n_steps, double dt, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((M + 255) / 256);
+    if (f32) hipLaunchKernelGGL(advance_obstacle_table_kernel<float>, dim3(blocks), dim3(256), 0, stream, (float*)table, M, n_steps, dt);
+    else hipLaunchKernelGGL(advance_obstacle_table_kernel<double>, dim3(blocks), dim3(256), 0, stream, (double*)table, M, n_steps, dt);
+    return hipGetLastError();
+}
+
 template <typename TIO, typename TC, int G, int MODEL>
 static hipError_t launch_track_coop(const sc_tracking_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                                     int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
@@ -792,10 +800,7 @@ hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void
     hipError_t e = f32 ? launch_track_m<float, double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream)
                        : launch_track_m<double, double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
     if (e != hipSuccess || !p.dyn_obs || M == 0) return e;
-    const unsigned blocks = (unsigned)((M + 255) / 256);
-    if (f32) hipLaunchKernelGGL(advance_obstacle_table_kernel<float>, dim3(blocks), dim3(256), 0, stream, (float*)table, M, p.n_steps, p.qp.dt);
-    else hipLaunchKernelGGL(advance_obstacle_table_kernel<double>, dim3(blocks), dim3(256), 0, stream, (double*)table, M, p.n_steps, p.qp.dt);
-    return hipGetLastError();
+    return advance_obstacle_table_launch(f32, table, M, p.n_steps, p.qp.dt, stream);
 }
 
 // ======================================================================================

@@ -33,6 +33,15 @@ def default_od_param(model):
     raise NotCompatibleError("Infeasible or Collision")
 
 
+def apply_od_overrides(cbf_param, robot_spec):
+    """cbf_qp.apply_cbf_overrides extended to the decay references and penalties: robot_spec keys cbf_alpha, cbf_alpha1, cbf_alpha2,
+    cbf_omega1, cbf_omega2, cbf_p_sb1, cbf_p_sb2 replace the entries the model's parameter set has."""
+    for key in ("alpha", "alpha1", "alpha2", "omega1", "omega2", "p_sb1", "p_sb2"):
+        if "cbf_" + key in robot_spec and key in cbf_param:
+            cbf_param[key] = float(robot_spec["cbf_" + key])
+    return cbf_param
+
+
 def make_od_params(robot_spec, cbf_param, dt, radius, io_dtype, compute_dtype):
     p = _lib.OdCbfQpParams()
     p.qp = make_params(robot_spec, cbf_param, dt, radius, io_dtype, compute_dtype)

@@ -20,7 +20,12 @@ import numpy as np
 
 from . import _lib
 from .position_control.cbf_qp import apply_cbf_overrides, default_cbf_param, make_params
+from .position_control.optimal_decay_cbf_qp import apply_od_overrides, default_od_param
 from .robots.spec import complete_robot_spec
+
+
+# the four-state models csrc/od_cbf_qp.hip has (Quad2D flies through the select / apply loop of BatchedQuadTrackingController)
+OD_QP_MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF")
 
 
 def _wrap(a):
@@ -34,6 +39,11 @@ class BatchedTrackingController:
     ``control_step(n=1)`` advances every running agent ``n`` steps and returns the per-agent return
     codes (0 running, -1 all waypoints reached, -2 infeasible QP or collision; sticky), like
     ``LocalTrackingController.control_step`` does for one robot.
+
+    ``controller_type={'pos': 'optimal_decay_cbf_qp'}`` (DynamicUnicycle2D and the KinematicBicycle2D family; ``dyn_obs``
+    allowed) runs the fused rollout of csrc/tracking_od.hip; ``cbf_param`` then holds the optimal-decay parameters
+    (``robot_spec`` keys cbf_alpha*, cbf_omega1/2, cbf_p_sb1/2 override them) and ``self.omega`` / ``self.min_h`` the decay
+    multipliers of every agent's last solve and the smallest barrier value it met.
     """
 
     def __new__(cls, X0, robot_spec, *args, **kwargs):
@@ -47,9 +57,10 @@ class BatchedTrackingController:
         self.torch = torch
         controller_type = controller_type or {"pos": "cbf_qp"}
         self.pos_controller_type = controller_type.get("pos", "cbf_qp")           # tracking.py:140-154
-        if self.pos_controller_type not in ("cbf_qp", "mpc_cbf", "optimal_decay_mpc_cbf"):
-            raise ValueError("position controllers of the batched loop: 'cbf_qp' (fused rollout), 'mpc_cbf', "
+        if self.pos_controller_type not in ("cbf_qp", "optimal_decay_cbf_qp", "mpc_cbf", "optimal_decay_mpc_cbf"):
+            raise ValueError("position controllers of the batched loop: 'cbf_qp', 'optimal_decay_cbf_qp' (fused rollouts), 'mpc_cbf', "
                              "'optimal_decay_mpc_cbf' (select / solve / apply per step)")
+        self.od_qp = self.pos_controller_type == "optimal_decay_cbf_qp"
         self.robot_spec = complete_robot_spec(robot_spec)
         self.robot_spec.setdefault("exploration", False)
         self.model = self.robot_spec["model"]
@@ -61,6 +72,8 @@ class BatchedTrackingController:
         self.integrator = self.model in ("SingleIntegrator2D", "DoubleIntegrator2D")
         if self.integrator and enable_rotation:
             raise ValueError("SingleIntegrator2D / DoubleIntegrator2D run with enable_rotation=False")
+        if self.od_qp and self.model not in OD_QP_MODELS:             # optimal_decay_cbf_qp.py:46-50 raises NotCompatibleError
+            raise ValueError(f"'optimal_decay_cbf_qp' is not compatible with model {self.model!r} (supported: {OD_QP_MODELS})")
         if self.integrator and self.pos_controller_type not in ("cbf_qp", "mpc_cbf"):
             raise ValueError("integrators: 'cbf_qp' or 'mpc_cbf' (SingleIntegrator2D: csrc/mpc_lin.hip, DoubleIntegrator2D: csrc/mpc_gn.hip)")
         self.dt = float(dt)
@@ -73,7 +86,10 @@ class BatchedTrackingController:
         self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))    # tracking.py:49-54
         self.rotation_threshold = 0.1                                                    # tracking.py:46
         self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))      # robots/robot.py:53-54
-        self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
+        if self.od_qp:
+            self.cbf_param = apply_od_overrides(default_od_param(self.model), self.robot_spec)
+        else:
+            self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
         self._lib = _lib.load()
 
         X0 = np.asarray(X0, dtype=np.float64)
@@ -100,7 +116,13 @@ class BatchedTrackingController:
         self.n_wp = None
         self.steps_done = 0
         self.mpc = None
-        if self.pos_controller_type != "cbf_qp":
+        if self.od_qp:
+            # the decay multipliers of every agent's last solve (at their references before the first) and the running minimum of
+            # the selected obstacle's h over the steps the agent took with an obstacle present
+            ref = [float(self.cbf_param.get("omega1", 1.0)), float(self.cbf_param.get("omega2", 1.0))]
+            self.omega = torch.tensor([ref] * self.B, dtype=self.tdtype, device=self.device).contiguous()
+            self.min_h = torch.full((self.B,), float("inf"), dtype=self.tdtype, device=self.device)
+        elif self.pos_controller_type != "cbf_qp":
             if self.dyn_obs:
                 raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' rollout only")
             from .position_control.mpc_cbf import BatchedMPCCBF
@@ -229,6 +251,24 @@ class BatchedTrackingController:
         p.wheel_base = float(rs.get("wheel_base", 0.0))
         return p
 
+    def _od_params(self, n_steps):
+        """sc_tracking_od_params: 'track' runs nominal_input(goal, k_omega=3.0, k_a=0.5, k_v=0.5) (tracking.py:601-602), which the
+        spec's nominal_k_* override for DynamicUnicycle2D only (dynamic_unicycle2D.py:84-86; the KinematicBicycle2D family takes the
+        forwarded gains as they are, robots/robot.py:406-407); stop() brakes with nominal_k_a or 1.0 (dynamic_unicycle2D.py:106-108)."""
+        rs = self.robot_spec
+        p = _lib.TrackingOdParams()
+        p.track = self._params(n_steps)
+        du = self.model == "DynamicUnicycle2D"
+        p.track.k_omega = float(rs.get("nominal_k_omega", 3.0)) if du else 3.0
+        p.track.k_a = float(rs.get("nominal_k_a", 0.5)) if du else 0.5
+        p.track.k_v = float(rs.get("nominal_k_v", 0.5)) if du else 0.5
+        p.k_a_stop = float(rs.get("nominal_k_a", 1.0)) if du else 1.0
+        p.omega_ref[0] = float(self.cbf_param.get("omega1", 1.0))
+        p.omega_ref[1] = float(self.cbf_param.get("omega2", 1.0))
+        p.p_sb[0] = float(self.cbf_param.get("p_sb1", 1e4))
+        p.p_sb[1] = float(self.cbf_param.get("p_sb2", 1e4))
+        return p
+
     # -- stepping -------------------------------------------------------------------------------
     def control_step(self, n=1, record=False):
         """Advance ``n`` control steps in one launch.  Returns ``ret`` [B] (and ``(traj_X [n,B,4],
@@ -238,6 +278,8 @@ class BatchedTrackingController:
             raise RuntimeError("call set_waypoints first")
         if self.mpc is not None:
             return self._control_step_split(n, record)
+        if self.od_qp:
+            return self._control_step_od(n, record)
         p = self._params(n)
         tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
         tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
@@ -251,6 +293,26 @@ class BatchedTrackingController:
         _lib.check(rc, "sc_tracking_rollout_batch")
         self.steps_done += n
         return (self.ret, tX, tU) if record else self.ret
+
+    def _control_step_od(self, n, record):
+        """control_step under 'optimal_decay_cbf_qp': one launch of csrc/tracking_od.hip.  With ``record`` returns
+        ``(ret, traj_X [n,B,4], traj_U [n,B,2], traj_omega [n,B,2])``; ``self.omega`` / ``self.min_h`` carry across launches."""
+        torch = self.torch
+        p = self._od_params(n)
+        tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
+        tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
+        tW = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sc_tracking_od_rollout_batch(
+            C.byref(p), self.B, int(self.obs.shape[0]), self.X.data_ptr(), self.waypoints.data_ptr(),
+            self.n_wp.data_ptr(), self.current_goal_index.data_ptr(), self.state_machine.data_ptr(),
+            self.goal.data_ptr(), self.obs.data_ptr() if self.obs.shape[0] else None, self.u_pos.data_ptr(),
+            self.ret.data_ptr(), self.ret_step.data_ptr(),
+            tX.data_ptr() if record else None, tU.data_ptr() if record else None,
+            self.omega.data_ptr(), self.min_h.data_ptr(), tW.data_ptr() if record else None, stream)
+        _lib.check(rc, "sc_tracking_od_rollout_batch")
+        self.steps_done += n
+        return (self.ret, tX, tU, tW) if record else self.ret
 
     def _dummy_rows(self, like):
         """[1000, 1000, 0, 0, 0, 0, 0] rows (update_tvp's padding, mpc_cbf.py:360) in the shape of one obstacle selection."""
