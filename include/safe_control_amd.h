@@ -767,6 +767,44 @@ int sc_tracking_od_rollout_batch(const sc_tracking_od_params* params, int64_t B,
                                  void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
                                  void* traj_X, void* traj_U, void* omega, void* min_h, void* traj_omega, void* stream);
 
+/* The fused loop for Quad2D (robots/quad2D.py; examples/test_tracking.py --model quad --algo cbf_qp, dynamic_env/main.py:314) under the
+ * two QP position controllers (kernel csrc/tracking_quad_qp.hip).  One launch = n_steps iterations of control_step, one agent per lane:
+ *   state machine  Quad2D leaves 'rotate' at once (tracking.py:512-513); has_stopped is hypot(vx, vz) < 0.05 (quad2D.py:156-158)
+ *   selection      the unpassed cone is the full circle: rows ordered by centre distance, the lower index wins a tie.  'cbf_qp' takes the
+ *                  od.track.num_constraints nearest, 'optimal_decay_cbf_qp' the nearest only
+ *   reference      Quad2D.nominal_input at its default gains under BOTH controllers (robots/robot.py:410-413 drops the gains that
+ *                  tracking.py:602 passes); with no goal stop() = nominal_input towards the own position (quad2D.py:145-154)
+ *   'cbf_qp'       rows [a, a] u + c >= 0 (cbf_qp.py:167-183, cbf_mode applies), box [f_min, f_max]^2, solved in every state-machine state;
+ *                  M == 0 returns u_ref unsolved with status optimal (cbf_qp.py:113-118)
+ *   'optimal_decay_cbf_qp'  one row and the two decay variables (optimal_decay_cbf_qp.py:38-45,104-115,131-158); M == 0 still solves, with
+ *                  a zero row; omega / min_h as in sc_tracking_od_rollout_batch
+ *   step           Euler step and the wrap of theta (quad2D.py:83-86); collision tests cover circles and superellipsoids
+ * Arithmetic is f64; storage follows od.track.qp.io_dtype.
+ */
+#define SC_QUAD2D_CTRL_CBF_QP    0
+#define SC_QUAD2D_CTRL_OD_CBF_QP 1
+typedef struct sc_tracking_quad2d_params {
+    sc_tracking_od_params od;  /* od.track.qp.model_id = SC_MODEL_QUAD2D, state_dim = 6, u_min/u_max = f_min/f_max;
+                                  omega_ref / p_sb read only under OD; k_* / v_* / delta_max / wheel_base / k_a_stop unused */
+    int32_t controller;        /* SC_QUAD2D_CTRL_* */
+    int32_t reserved0;         /* keep 0 */
+    double  inertia;           /* robot_spec['inertia'] */
+} sc_tracking_quad2d_params;
+
+/* X [B,6] in/out = [x, z, theta, vx, vz, theta_dot]; waypoints [B,W,2] (or [W,2]), n_wp, wp_index, state_machine, goal [B,3], obs_table [M,7],
+ * u_last [B,2], ret, ret_step as in sc_tracking_rollout_batch; traj_X [n_steps,B,6], traj_U [n_steps,B,2] optional.  omega [B,2], min_h [B]
+ * (required) and traj_omega [n_steps,B,2] (optional) as in sc_tracking_od_rollout_batch under SC_QUAD2D_CTRL_OD_CBF_QP; all three are
+ * ignored under SC_QUAD2D_CTRL_CBF_QP and may be NULL there.  Frozen agents repeat their last values in the traj_* rows.
+ * Every argument is checked before the first HIP call; B == 0 and n_steps == 0 return SC_OK.  SC_ERR_UNSUPPORTED: a model other than Quad2D,
+ * an unknown controller.  SC_ERR_INVALID_ARGUMENT: NULL required pointers, M > 0 without a table, mass / inertia / robot_radius / dt not
+ * finite and positive, f_min > f_max, num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS] under 'cbf_qp', p_sb not positive under OD,
+ * a bad io_dtype, max_waypoints < 1. */
+int sc_tracking_quad2d_rollout_batch(const sc_tracking_quad2d_params* params, int64_t B, int32_t M,
+                                     void* X, const void* waypoints, const int32_t* n_wp,
+                                     int32_t* wp_index, int32_t* state_machine, void* goal,
+                                     void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
+                                     void* traj_X, void* traj_U, void* omega, void* min_h, void* traj_omega, void* stream);
+
 /* control_step split around the solve, for position controllers that are their own launch (MPC-CBF, optimal-decay
  * MPC-CBF; the reference's default `--algo mpc_cbf`, examples/test_tracking.py:15):
  *   sc_tracking_select_batch = tracking.py:569-609: state machine / goal update, nearest-unpassed selection

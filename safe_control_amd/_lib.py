@@ -346,6 +346,14 @@ class TrackingOdParams(C.Structure):
                 ("k_a_stop", C.c_double), ("reserved", C.c_double)]
 
 
+QUAD2D_CTRL_CBF_QP, QUAD2D_CTRL_OD_CBF_QP = 0, 1                                             # SC_QUAD2D_CTRL_*
+
+
+class TrackingQuad2dParams(C.Structure):
+    """Mirror of ``sc_tracking_quad2d_params``."""
+    _fields_ = [("od", TrackingOdParams), ("controller", C.c_int32), ("reserved0", C.c_int32), ("inertia", C.c_double)]
+
+
 ATT_NONE, ATT_SIMPLE, ATT_VELOCITY_TRACKING_YAW = 0, 1, 2                                   # SC_ATT_*
 SENSE_MAX_UNKNOWN = 64                                                                       # SC_SENSE_MAX_UNKNOWN
 
@@ -428,6 +436,7 @@ SYMBOLS = {
     "sc_drift_shield_rollout_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "sc_tracking_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_od_rollout_batch": (C.c_int, [C.POINTER(TrackingOdParams), C.c_int64, C.c_int32] + [C.c_void_p] * 16),
+    "sc_tracking_quad2d_rollout_batch": (C.c_int, [C.POINTER(TrackingQuad2dParams), C.c_int64, C.c_int32] + [C.c_void_p] * 16),
     "sc_tracking_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
     "sc_tracking_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 10),
     "sc_tracking_fleet_step_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32, C.c_int32, C.c_int32]

@@ -42,6 +42,9 @@ hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void
 hipError_t tracking_od_launch(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                               int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                               void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream);
+hipError_t tracking_quad2d_launch(const sc_tracking_quad2d_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
+                                  int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
+                                  void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream);
 hipError_t tracking_fleet_launch(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
                                  const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, void* table,
                                  const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream);
@@ -1430,6 +1433,43 @@ int sc_tracking_od_rollout_batch(const sc_tracking_od_params* params, int64_t B,
     hipError_t e = sc::tracking_od_launch(*params, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal, obs_table,
                                           u_last, ret, ret_step, traj_X, traj_U, omega, min_h, traj_omega, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "optimal-decay tracking kernel launch");
+    return SC_OK;
+}
+
+int sc_tracking_quad2d_rollout_batch(const sc_tracking_quad2d_params* params, int64_t B, int32_t M, void* X, const void* waypoints,
+                                     const int32_t* n_wp, int32_t* wp_index, int32_t* state_machine, void* goal, void* obs_table,
+                                     void* u_last, int32_t* ret, int32_t* ret_step, void* traj_X, void* traj_U, void* omega,
+                                     void* min_h, void* traj_omega, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    const sc_tracking_od_params* o = &params->od;
+    const sc_tracking_params* t = &o->track;
+    const sc_cbfqp_params* q = &t->qp;
+    if (B < 0 || M < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0 or M < 0");
+    if (q->model_id != SC_MODEL_QUAD2D) return sc::fail(SC_ERR_UNSUPPORTED, "the Quad2D rollout is built for SC_MODEL_QUAD2D only");
+    if (params->controller != SC_QUAD2D_CTRL_CBF_QP && params->controller != SC_QUAD2D_CTRL_OD_CBF_QP)
+        return sc::fail(SC_ERR_UNSUPPORTED, "controller must be SC_QUAD2D_CTRL_CBF_QP or SC_QUAD2D_CTRL_OD_CBF_QP");
+    const bool od = params->controller == SC_QUAD2D_CTRL_OD_CBF_QP;
+    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (t->n_steps < 0 || t->max_waypoints < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_steps < 0 or max_waypoints < 1");
+    auto positive = [](double v) { return std::isfinite(v) && v > 0; };
+    if (!positive(q->mass) || !positive(params->inertia) || !positive(q->robot_radius) || !positive(q->dt))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "mass, inertia, robot_radius and dt must be finite and > 0");
+    if (!(q->u_min[0] <= q->u_max[0]) || !(q->u_min[1] <= q->u_max[1])) return sc::fail(SC_ERR_INVALID_ARGUMENT, "f_min > f_max");
+    if (!od && (t->num_constraints < 1 || t->num_constraints > SC_TRACKING_MAX_CONSTRAINTS))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
+    if (od && (!(o->p_sb[0] > 0) || !(o->p_sb[1] > 0))) return sc::fail(SC_ERR_INVALID_ARGUMENT, "p_sb must be > 0");
+    if ((size_t)M * 7 * 8 > 160 * 1024) return sc::fail(SC_ERR_UNSUPPORTED, "obstacle table does not fit the LDS");
+    if (B > 0 && (!X || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !u_last || !ret || !ret_step ||
+                  (od && (!omega || !min_h)) || (M > 0 && !obs_table)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B == 0 || t->n_steps == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_quad2d_launch(*params, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal, obs_table,
+                                              u_last, ret, ret_step, traj_X, traj_U, od ? omega : nullptr, od ? min_h : nullptr,
+                                              od ? traj_omega : nullptr, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "Quad2D tracking kernel launch");
     return SC_OK;
 }
 

@@ -24,8 +24,10 @@ from .position_control.optimal_decay_cbf_qp import apply_od_overrides, default_o
 from .robots.spec import complete_robot_spec
 
 
-# the four-state models csrc/od_cbf_qp.hip has (Quad2D flies through the select / apply loop of BatchedQuadTrackingController)
+# the four-state models of csrc/tracking_od.hip (Quad2D flies through BatchedQuadTrackingController)
 OD_QP_MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF")
+# Quad2D's fused rollouts (csrc/tracking_quad_qp.hip); its default stays 'mpc_cbf'
+QUAD2D_QP_CONTROLLERS = ("cbf_qp", "optimal_decay_cbf_qp")
 
 
 def _wrap(a):
@@ -412,6 +414,12 @@ class BatchedQuadTrackingController(BatchedTrackingController):
     """The batched closed loop for Quad2D (examples/test_tracking.py --model quad), Quad3D (--model quad3d) and VTOL2D
     (examples/test_vtol.py) with the reference's default position controller ``mpc_cbf``: per step  sc_quadtrack_select_batch -> one
     MPC-CBF launch for the batch (csrc/mpc_gn.hip / csrc/mpc_lin.hip / csrc/mpc_vtol_wave.hip) -> sc_quadtrack_apply_batch.
+    Quad2D also flies under ``controller_type={'pos': 'cbf_qp'}`` and ``{'pos': 'optimal_decay_cbf_qp'}`` (examples/test_tracking.py
+    --model quad --algo cbf_qp; dynamic_env/main.py:314): ``control_step(n, record)`` is then ONE launch of the fused rollout
+    csrc/tracking_quad_qp.hip, ``dyn_obs`` is allowed, ``cbf_param`` holds the controller's gains (``robot_spec`` keys cbf_alpha1/2,
+    cbf_omega1/2, cbf_p_sb1/2 override them), no MPC object exists, ``waypoints`` is [B,W,2] and ``goal`` [B,3] as on
+    ``BatchedTrackingController``; under optimal decay ``self.omega`` / ``self.min_h`` exist and ``record`` also returns
+    ``traj_omega``.  Quad3D and VTOL2D have no CBF-QP barrier in the reference (quad3D.py:269-273) and keep raising.
     VTOL2D: ``X0`` rows [x, z(, .)] (cruise at 5 m/s, tracking.py:94-99) or six states.  ``X0`` rows follow tracking.py:80-93 (Quad2D:
     [x, z(, .)] or six states; Quad3D: [x, y], [x, y, yaw], [x, y, z, yaw] or twelve states); waypoints are [x, y, z] rows for
     Quad3D (the example's third column -- a heading for the planar models -- is the altitude goal there, tracking.py:501-502)."""
@@ -422,21 +430,28 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         self.torch = torch
         controller_type = controller_type or {"pos": "mpc_cbf"}
         self.pos_controller_type = controller_type.get("pos", "mpc_cbf")
-        if self.pos_controller_type != "mpc_cbf":
-            raise ValueError("Quad2D / Quad3D / VTOL2D closed loop: position controller 'mpc_cbf' (the reference's default)")
-        if dyn_obs:
-            raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' rollout only")
         self.model = robot_spec["model"]
+        self.qp_ctrl = self.pos_controller_type in QUAD2D_QP_CONTROLLERS
+        self.od_qp = self.pos_controller_type == "optimal_decay_cbf_qp"
+        if self.qp_ctrl and self.model != "Quad2D":
+            raise ValueError(f"{self.model} closed loop: position controller 'mpc_cbf' (the reference has no CBF-QP barrier for it)")
+        if self.pos_controller_type != "mpc_cbf" and not self.qp_ctrl:
+            raise ValueError("Quad2D closed loop: position controllers 'mpc_cbf' (the reference's default), 'cbf_qp', "
+                             "'optimal_decay_cbf_qp'; Quad3D / VTOL2D: 'mpc_cbf'")
+        if dyn_obs and not self.qp_ctrl:
+            raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' / 'optimal_decay_cbf_qp' rollouts only")
         self.q3 = self.model == "Quad3D"
         self.vt = self.model == "VTOL2D"
         self.robot_spec = complete_robot_spec(robot_spec)
         self.robot_spec.setdefault("exploration", False)
         self.integrator = False
-        self.dt, self.enable_rotation, self.dyn_obs = float(dt), bool(enable_rotation), False
+        self.dt, self.enable_rotation, self.dyn_obs = float(dt), bool(enable_rotation), bool(dyn_obs)
         self.device = torch.device(device)
         self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]
         self.tdtype = torch.float32 if io_dtype == "f32" else torch.float64
         self.num_constraints = int(self.robot_spec.get("num_constraints", 10))
+        if self.qp_ctrl and not self.od_qp and not 1 <= self.num_constraints <= _lib.TRACKING_MAX_CONSTRAINTS:
+            raise ValueError(f"num_constraints must be in [1, {_lib.TRACKING_MAX_CONSTRAINTS}]")
         self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))
         self.rotation_threshold = 0.1
         self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))
@@ -479,13 +494,23 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         self.X = t(X)
         self.state_machine = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.current_goal_index = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.goal = torch.zeros((B, 4), dtype=self.tdtype, device=self.device)            # gx, gy, gz, valid
+        self.goal = torch.zeros((B, 3 if self.qp_ctrl else 4), dtype=self.tdtype, device=self.device)   # gx, gy, (gz,) valid
         self.ret = torch.zeros(B, dtype=torch.int32, device=self.device)
         self.ret_step = torch.full((B,), -1, dtype=torch.int32, device=self.device)
         self.u_pos = torch.zeros((B, self.nu), dtype=self.tdtype, device=self.device)
         self.set_obstacles(obs)
         self.waypoints = self.n_wp = None
         self.steps_done = 0
+        self.mpc = None
+        if self.qp_ctrl:                                       # the fused rollout of csrc/tracking_quad_qp.hip: no MPC object
+            if self.od_qp:
+                self.cbf_param = apply_od_overrides(default_od_param(self.model), self.robot_spec)
+                ref = [float(self.cbf_param.get("omega1", 1.0)), float(self.cbf_param.get("omega2", 1.0))]
+                self.omega = torch.tensor([ref] * B, dtype=self.tdtype, device=self.device).contiguous()
+                self.min_h = torch.full((B,), float("inf"), dtype=self.tdtype, device=self.device)
+            else:
+                self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
+            return
         if self.q3:
             from .position_control.mpc_cbf_linear import BatchedLinearMPCCBF as cls
         elif self.vt:
@@ -504,6 +529,13 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         self.mpc = cls(self.robot_spec, dt=self.dt, io_dtype=io_dtype, **kw)
         self.u_prev = torch.zeros((B, self.nu), dtype=self.tdtype, device=self.device)
         self.mpc_status = torch.zeros(B, dtype=torch.int32, device=self.device)
+
+    def set_obstacles(self, obs):
+        super().set_obstacles(obs)
+        if self.qp_ctrl and self.obs_has_superellipsoid:
+            # Quad2D.agent_barrier has the circle branch only (quad2D.py:166-177): it would read obs[2] of such a row as a radius
+            raise ValueError("Quad2D under 'cbf_qp' / 'optimal_decay_cbf_qp': the obstacle table holds a superellipsoid row "
+                             "(column 6 >= 0.5), for which Quad2D has no barrier")
 
     def set_waypoints(self, waypoints):
         """set_waypoints / filter_waypoints / first update_goal (tracking.py:197-262, 497-535) on the host."""
@@ -556,8 +588,54 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         self.current_goal_index = torch.tensor(idx, dtype=torch.int32, device=self.device)
         self.state_machine = torch.tensor(sm, dtype=torch.int32, device=self.device)
         self.goal = torch.tensor(goal, dtype=self.tdtype, device=self.device).contiguous()
+        if self.qp_ctrl:                                       # the fused rollout takes planar rows: [B,W,2] and (gx, gz, valid)
+            self.waypoints = self.waypoints[:, :, :2].contiguous()
+            self.goal = self.goal[:, [0, 1, 3]].contiguous()
         self.ret.zero_()
         self.ret_step.fill_(-1)
+
+    def _qp_params(self, n_steps):
+        """sc_tracking_quad2d_params.  The nominal input runs at Quad2D's own gains under both controllers (robots/robot.py:410-413 drops
+        the k_omega / k_a / k_v that tracking.py:602 passes), so the gain fields stay zero."""
+        rs = self.robot_spec
+        p = _lib.TrackingQuad2dParams()
+        t = p.od.track
+        t.qp = make_params(rs, self.cbf_param, self.dt, rs["radius"], self.io_dtype, _lib.DTYPE_F64)
+        t.n_steps, t.step_offset = int(n_steps), int(self.steps_done)
+        t.max_waypoints, t.waypoints_shared = int(self.waypoints.shape[1]), 0
+        t.enable_rotation = 1 if self.enable_rotation else 0
+        t.dyn_obs = 1 if self.dyn_obs else 0
+        t.num_constraints = self.num_constraints
+        t.reached_threshold, t.rotation_threshold = self.reached_threshold, self.rotation_threshold
+        p.od.omega_ref[0] = float(self.cbf_param.get("omega1", 1.0))
+        p.od.omega_ref[1] = float(self.cbf_param.get("omega2", 1.0))
+        p.od.p_sb[0] = float(self.cbf_param.get("p_sb1", 1e4))
+        p.od.p_sb[1] = float(self.cbf_param.get("p_sb2", 1e4))
+        p.controller = _lib.QUAD2D_CTRL_OD_CBF_QP if self.od_qp else _lib.QUAD2D_CTRL_CBF_QP
+        p.inertia = float(rs["inertia"])
+        return p
+
+    def _control_step_qp(self, n, record):
+        """control_step under 'cbf_qp' / 'optimal_decay_cbf_qp': one launch of csrc/tracking_quad_qp.hip.  With ``record`` returns
+        ``(ret, traj_X [n,B,6], traj_U [n,B,2])`` and, under optimal decay, ``traj_omega [n,B,2]`` as a fourth entry."""
+        torch = self.torch
+        p = self._qp_params(n)
+        B, M = self.B, int(self.obs.shape[0])
+        new = lambda w: torch.empty((n, B, w), dtype=self.tdtype, device=self.device)
+        tX, tU = (new(6), new(2)) if record else (None, None)
+        tW = new(2) if (record and self.od_qp) else None
+        ptr = lambda a: a.data_ptr() if a is not None else None
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.sc_tracking_quad2d_rollout_batch(
+            C.byref(p), B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(), self.current_goal_index.data_ptr(),
+            self.state_machine.data_ptr(), self.goal.data_ptr(), self.obs.data_ptr() if M else None, self.u_pos.data_ptr(),
+            self.ret.data_ptr(), self.ret_step.data_ptr(), ptr(tX), ptr(tU),
+            self.omega.data_ptr() if self.od_qp else None, self.min_h.data_ptr() if self.od_qp else None, ptr(tW), stream)
+        _lib.check(rc, "sc_tracking_quad2d_rollout_batch")
+        self.steps_done += n
+        if not record:
+            return self.ret
+        return (self.ret, tX, tU, tW) if self.od_qp else (self.ret, tX, tU)
 
     def _params(self, n_steps=1):
         rs = self.robot_spec
@@ -600,6 +678,8 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         torch = self.torch
         if self.waypoints is None:
             raise RuntimeError("call set_waypoints first")
+        if self.qp_ctrl:
+            return self._control_step_qp(n, record)
         p = self._params()
         M, K, B = int(self.obs.shape[0]), self.num_constraints, self.B
         obs_sel = torch.empty((B, K, 7), dtype=self.tdtype, device=self.device)
