@@ -12,6 +12,13 @@ detection, sensing footprints (return code 1), the 'visibility_*' and 'gatekeepe
 
 Host side (this file) only prepares waypoints the way ``set_waypoints`` / ``filter_waypoints`` do
 (tracking.py:197-249) and owns the device tensors.  No CPU fallback.
+
+Every class shares one copy of the host logic, all of it on ``BatchedTrackingController``: construction
+(``_configure``, then the class's own checks and ``X0`` unpacking, then ``_allocate``), waypoint
+preparation (``set_waypoints``, told apart by ``npos`` / ``wp_cols`` / ``_headings``), the fill of
+``sc_tracking_params`` (``_tracking_params``, which ``_od_params`` and ``_qp_params`` fill their member with), the launch of a
+fused rollout (``_rollout``) and the select / solve / apply loop of the MPC controllers
+(``_control_step_split``).
 """
 import ctypes as C
 import math
@@ -30,8 +37,19 @@ OD_QP_MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "KinematicBicycle2D_C
 QUAD2D_QP_CONTROLLERS = ("cbf_qp", "optimal_decay_cbf_qp")
 
 
+# what a fused rollout records besides traj_X / traj_U: the (trailing shape, dtype or None for the loop's own) of one [n,B,...] buffer each
+TRAJ_OMEGA = (((2,), None),)                                   # traj_omega [n,B,2]
+TRAJ_YAW_SEEN = (((), None), ((), "int64"))                    # traj_yaw [n,B], traj_seen [n,B] int64
+
+
 def _wrap(a):
     return ((a + math.pi) % (2.0 * math.pi)) - math.pi
+
+
+def _shared_list(waypoints):
+    """True for one list of [x, y(, theta)] rows shared by every agent, False for one such list per agent."""
+    return (isinstance(waypoints, np.ndarray) and waypoints.ndim == 2) or \
+        (isinstance(waypoints, (list, tuple)) and len(waypoints) > 0 and np.ndim(waypoints[0]) == 1)
 
 
 class BatchedTrackingController:
@@ -53,46 +71,34 @@ class BatchedTrackingController:
             return super().__new__(BatchedQuadTrackingController)      # 6 / 12 states, 2 / 4 inputs: its own select / apply kernels
         return super().__new__(cls)
 
+    # widths of a state row, an input row and a goal handed to the MPC; the position columns that waypoint filtering measures and the
+    # columns of a stored waypoint row (``goal`` has one more: valid)
+    nx, nu, ng, npos, wp_cols = 4, 2, 2, 2, 2
+    # the per-step entry points of the MPC loop, and what sc_tracking_apply_batch takes between the input and ``u_pos``
+    _SPLIT = ("sc_tracking_select_batch", "sc_tracking_apply_batch", (None,))
+    # whether sc_tracking_params carries the speed bounds, the gains of nominal_input and the bicycle's geometry
+    _nominal_gains = True
+
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None,
                  dyn_obs=False, io_dtype="f64", device="cuda:0"):
-        import torch
-        self.torch = torch
         controller_type = controller_type or {"pos": "cbf_qp"}
         self.pos_controller_type = controller_type.get("pos", "cbf_qp")           # tracking.py:140-154
         if self.pos_controller_type not in ("cbf_qp", "optimal_decay_cbf_qp", "mpc_cbf", "optimal_decay_mpc_cbf"):
             raise ValueError("position controllers of the batched loop: 'cbf_qp', 'optimal_decay_cbf_qp' (fused rollouts), 'mpc_cbf', "
                              "'optimal_decay_mpc_cbf' (select / solve / apply per step)")
         self.od_qp = self.pos_controller_type == "optimal_decay_cbf_qp"
-        self.robot_spec = complete_robot_spec(robot_spec)
-        self.robot_spec.setdefault("exploration", False)
-        self.model = self.robot_spec["model"]
+        self._configure(robot_spec, dt, enable_rotation, dyn_obs, io_dtype, device)
         if self.model not in _lib.MODEL_IDS or self.model == "Quad2D":
             raise ValueError(f"the batched closed loop does not support model {self.model!r}")
         # the integrators keep their heading outside the state (robots/robot.py:66-72); their rotate state runs the
         # attitude controllers, which this class does not have (BatchedSensingTrackingController does): enable_rotation
         # must be off and the heading then never changes
-        self.integrator = self.model in ("SingleIntegrator2D", "DoubleIntegrator2D")
         if self.integrator and enable_rotation:
             raise ValueError("SingleIntegrator2D / DoubleIntegrator2D run with enable_rotation=False")
         if self.od_qp and self.model not in OD_QP_MODELS:             # optimal_decay_cbf_qp.py:46-50 raises NotCompatibleError
             raise ValueError(f"'optimal_decay_cbf_qp' is not compatible with model {self.model!r} (supported: {OD_QP_MODELS})")
         if self.integrator and self.pos_controller_type not in ("cbf_qp", "mpc_cbf"):
             raise ValueError("integrators: 'cbf_qp' or 'mpc_cbf' (SingleIntegrator2D: csrc/mpc_lin.hip, DoubleIntegrator2D: csrc/mpc_gn.hip)")
-        self.dt = float(dt)
-        self.enable_rotation = bool(enable_rotation)
-        self.dyn_obs = bool(dyn_obs)
-        self.device = torch.device(device)
-        self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]
-        self.tdtype = torch.float32 if io_dtype == "f32" else torch.float64
-        self.num_constraints = int(self.robot_spec.get("num_constraints", 10))          # tracking.py:134-138
-        self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))    # tracking.py:49-54
-        self.rotation_threshold = 0.1                                                    # tracking.py:46
-        self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))      # robots/robot.py:53-54
-        if self.od_qp:
-            self.cbf_param = apply_od_overrides(default_od_param(self.model), self.robot_spec)
-        else:
-            self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
-        self._lib = _lib.load()
 
         X0 = np.asarray(X0, dtype=np.float64)
         if X0.ndim == 1:
@@ -104,55 +110,105 @@ class BatchedTrackingController:
             X0 = np.hstack([X0[:, :nst], np.zeros((X0.shape[0], 4 - nst))])
         elif X0.shape[1] == 3:                                 # tracking.py:66-68: initial speed 0
             X0 = np.hstack([X0, np.zeros((X0.shape[0], 1))])
-        self.B = X0.shape[0]
-        t = lambda a, dt_=None: torch.tensor(a, dtype=dt_ or self.tdtype, device=self.device)
-        self.X = t(X0)
-        self.state_machine = torch.zeros(self.B, dtype=torch.int32, device=self.device)      # 'idle'
-        self.current_goal_index = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.goal = torch.zeros((self.B, 3), dtype=self.tdtype, device=self.device)          # gx, gy, valid
-        self.ret = torch.zeros(self.B, dtype=torch.int32, device=self.device)
-        self.ret_step = torch.full((self.B,), -1, dtype=torch.int32, device=self.device)
-        self.u_pos = torch.zeros((self.B, 2), dtype=self.tdtype, device=self.device)
+        self._allocate(X0, obs)
+        if self.od_qp or self.pos_controller_type == "cbf_qp":
+            return
+        if self.dyn_obs:
+            raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' rollout only")
+        from .position_control.mpc_cbf import BatchedMPCCBF
+        from .position_control.optimal_decay_mpc_cbf import BatchedOptimalDecayMPCCBF
+        if self.model == "SingleIntegrator2D":             # linear model: csrc/mpc_lin.hip
+            from .position_control.mpc_cbf_linear import BatchedLinearMPCCBF
+            cls = BatchedLinearMPCCBF
+        elif self.model in ("DoubleIntegrator2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF"):
+            # barrier through the robot's own step(): csrc/mpc_gn.hip
+            if self.pos_controller_type != "mpc_cbf":
+                raise ValueError(f"{self.model}: 'cbf_qp' or 'mpc_cbf'")
+            from .position_control.mpc_cbf_gn import BatchedGnMPCCBF
+            cls = BatchedGnMPCCBF
+        else:
+            cls = BatchedMPCCBF if self.pos_controller_type == "mpc_cbf" else BatchedOptimalDecayMPCCBF
+        mpc = cls(self.robot_spec, dt=self.dt, io_dtype=io_dtype)
+        # DynamicUnicycle2D, Unicycle2D and DoubleIntegrator2D under 'mpc_cbf': the NLP as do-mpc poses it (multiple shooting, IPOPT's algorithm: csrc/mpc_du_ms.hip, kernel 13)
+        # unless robot_spec['mpc_formulation'] = 'condensed'; a scene with superellipsoid rows runs on the condensed kernel
+        mpc_ms = None
+        ms_model = (cls is BatchedMPCCBF and self.model in ("DynamicUnicycle2D", "Unicycle2D")) or (self.model == "DoubleIntegrator2D" and self.pos_controller_type == "mpc_cbf")
+        want = self.robot_spec.get("mpc_formulation", "multiple_shooting" if ms_model else "condensed")
+        if self.model == "KinematicBicycle2D" and self.pos_controller_type == "mpc_cbf":      # on request only (position_control/mpc_cbf_gn.py: GnMPCCBF)
+            ms_model = True
+        if ms_model and want == "multiple_shooting" and self.num_constraints <= 16:
+            from .position_control.mpc_cbf_ms import BatchedMSMPCCBF
+            mpc_ms = BatchedMSMPCCBF(self.robot_spec, dt=self.dt, io_dtype=io_dtype, check_circles=False)
+        self._init_split(mpc, mpc_ms)
+
+    def _configure(self, robot_spec, dt, enable_rotation, dyn_obs, io_dtype, device):
+        """The host half of construction, the same for every class: the completed spec, flags, dtypes, thresholds and the
+        library.  It creates no device tensor, so a class may still refuse its arguments after it."""
+        import torch
+        self.torch = torch
+        self.robot_spec = complete_robot_spec(robot_spec)
+        self.robot_spec.setdefault("exploration", False)
+        self.model = self.robot_spec["model"]
+        self.integrator = self.model in ("SingleIntegrator2D", "DoubleIntegrator2D")
+        self.dt = float(dt)
+        self.enable_rotation = bool(enable_rotation)
+        self.dyn_obs = bool(dyn_obs)
+        self.device = torch.device(device)
+        self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]
+        self.tdtype = torch.float32 if io_dtype == "f32" else torch.float64
+        self.num_constraints = int(self.robot_spec.get("num_constraints", 10))          # tracking.py:134-138
+        self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))    # tracking.py:49-54
+        self.rotation_threshold = 0.1                                                    # tracking.py:46
+        self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))      # robots/robot.py:53-54
+        self._lib = _lib.load()
+
+    def _allocate(self, X0, obs, cbf_qp=True):
+        """The device half: the state ``X0 [B,nx]`` as unpacked by the class, the per-agent tensors, the obstacle table and the
+        counters; with ``cbf_qp`` (a class that fills sc_tracking_params) ``cbf_param`` and, under 'optimal_decay_cbf_qp',
+        ``omega`` / ``min_h``."""
+        torch = self.torch
+        if self.od_qp:
+            self.cbf_param = apply_od_overrides(default_od_param(self.model), self.robot_spec)
+        elif cbf_qp:
+            self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
+        B = self.B = X0.shape[0]
+        self.X = torch.tensor(X0, dtype=self.tdtype, device=self.device)
+        self.state_machine = torch.zeros(B, dtype=torch.int32, device=self.device)      # 'idle'
+        self.current_goal_index = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.goal = torch.zeros((B, self.wp_cols + 1), dtype=self.tdtype, device=self.device)   # gx, gy, (gz,) valid
+        self.ret = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self.ret_step = torch.full((B,), -1, dtype=torch.int32, device=self.device)
+        self.u_pos = torch.zeros((B, self.nu), dtype=self.tdtype, device=self.device)
         self.set_obstacles(obs)
         self.waypoints = None
         self.n_wp = None
         self.steps_done = 0
-        self.mpc = None
+        self.mpc = self.mpc_ms = None
         if self.od_qp:
             # the decay multipliers of every agent's last solve (at their references before the first) and the running minimum of
             # the selected obstacle's h over the steps the agent took with an obstacle present
             ref = [float(self.cbf_param.get("omega1", 1.0)), float(self.cbf_param.get("omega2", 1.0))]
-            self.omega = torch.tensor([ref] * self.B, dtype=self.tdtype, device=self.device).contiguous()
-            self.min_h = torch.full((self.B,), float("inf"), dtype=self.tdtype, device=self.device)
-        elif self.pos_controller_type != "cbf_qp":
-            if self.dyn_obs:
-                raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' rollout only")
-            from .position_control.mpc_cbf import BatchedMPCCBF
-            from .position_control.optimal_decay_mpc_cbf import BatchedOptimalDecayMPCCBF
-            if self.model == "SingleIntegrator2D":             # linear model: csrc/mpc_lin.hip
-                from .position_control.mpc_cbf_linear import BatchedLinearMPCCBF
-                cls = BatchedLinearMPCCBF
-            elif self.model in ("DoubleIntegrator2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF"):
-                # barrier through the robot's own step(): csrc/mpc_gn.hip
-                if self.pos_controller_type != "mpc_cbf":
-                    raise ValueError(f"{self.model}: 'cbf_qp' or 'mpc_cbf'")
-                from .position_control.mpc_cbf_gn import BatchedGnMPCCBF
-                cls = BatchedGnMPCCBF
-            else:
-                cls = BatchedMPCCBF if self.pos_controller_type == "mpc_cbf" else BatchedOptimalDecayMPCCBF
-            self.mpc = cls(self.robot_spec, dt=self.dt, io_dtype=io_dtype)
-            # DynamicUnicycle2D, Unicycle2D and DoubleIntegrator2D under 'mpc_cbf': the NLP as do-mpc poses it (multiple shooting, IPOPT's algorithm: csrc/mpc_du_ms.hip, kernel 13)
-            # unless robot_spec['mpc_formulation'] = 'condensed'; a scene with superellipsoid rows runs on the condensed kernel
-            self.mpc_ms = None
-            ms_model = (cls is BatchedMPCCBF and self.model in ("DynamicUnicycle2D", "Unicycle2D")) or (self.model == "DoubleIntegrator2D" and self.pos_controller_type == "mpc_cbf")
-            want = self.robot_spec.get("mpc_formulation", "multiple_shooting" if ms_model else "condensed")
-            if self.model == "KinematicBicycle2D" and self.pos_controller_type == "mpc_cbf":      # on request only (position_control/mpc_cbf_gn.py: GnMPCCBF)
-                ms_model = True
-            if ms_model and want == "multiple_shooting" and self.num_constraints <= 16:
-                from .position_control.mpc_cbf_ms import BatchedMSMPCCBF
-                self.mpc_ms = BatchedMSMPCCBF(self.robot_spec, dt=self.dt, io_dtype=io_dtype, check_circles=False)
-            self.u_prev = torch.zeros((self.B, 2), dtype=self.tdtype, device=self.device)   # do-mpc's u0 per agent
-            self.mpc_status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+            self.omega = torch.tensor([ref] * B, dtype=self.tdtype, device=self.device).contiguous()
+            self.min_h = torch.full((B,), float("inf"), dtype=self.tdtype, device=self.device)
+
+    def _init_split(self, mpc, mpc_ms=None):
+        """What the select / solve / apply loop keeps between steps: do-mpc's u0 per agent, status and iteration count of every
+        agent's last solve, and the rows that stand in for the agents outside 'track' (see _control_step_split)."""
+        torch = self.torch
+        self.mpc, self.mpc_ms = mpc, mpc_ms
+        self.u_prev = torch.zeros((self.B, self.nu), dtype=self.tdtype, device=self.device)
+        self.mpc_status = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self.mpc_iters = torch.zeros(self.B, dtype=torch.int32, device=self.device)
+        self._raw_iters = self._raw_track = None               # what the last launch ran, slots outside 'track' included
+        xe, ge = self._easy_problem()
+        self._easy = (torch.tensor([xe], dtype=self.tdtype, device=self.device), torch.tensor([ge], dtype=self.tdtype, device=self.device))
+        self._u_zero = torch.zeros_like(self.u_prev)
+        # [1000, 1000, 0, 0, 0, 0, 0] rows (update_tvp's padding, mpc_cbf.py:360) in the shape of one obstacle selection.
+        # OptimalDecayMPCCBF has five fixed obstacle slots (optimal_decay_mpc_cbf.py:249-252,333-339: padded_obs[:5]):
+        # it sees the five nearest of the selected rows, MPCCBF all num_constraints of them
+        self._od_slots = self.pos_controller_type == "optimal_decay_mpc_cbf" and self.num_constraints > 5
+        self._dummy_obs = torch.zeros((1, 5 if self._od_slots else self.num_constraints, 7), dtype=self.tdtype, device=self.device)
+        self._dummy_obs[:, :, :2] = 1000.0
 
     # -- obstacles -----------------------------------------------------------------------------
     def set_obstacles(self, obs):
@@ -167,30 +223,38 @@ class BatchedTrackingController:
         self.obs = torch.tensor(obs[:, :7], dtype=self.tdtype, device=self.device).contiguous()
         self.obs_has_superellipsoid = bool((obs[:, 6] >= 0.5).any())
 
-    # -- waypoints: set_waypoints / filter_waypoints / first update_goal (tracking.py:197-249, 497-535) --
+    # -- waypoints: set_waypoints / filter_waypoints / first update_goal (tracking.py:197-262, 497-535) --
+    def _headings(self, X):
+        """Every agent's heading on the host, for the test whether its first goal is in view (robots/robot.py:854-872); None: always."""
+        return self.yaw if self.integrator else X[:, 2]
+
     def set_waypoints(self, waypoints):
+        """One list of [x, y(, theta)] rows shared by every agent, or one such list per agent ([x, y, z] rows for Quad3D)."""
         torch = self.torch
         X = self.X.double().cpu().numpy()
-        # one list of [x, y(, theta)] rows shared by every agent, or one such list per agent
-        shared = (isinstance(waypoints, np.ndarray) and waypoints.ndim == 2) or \
-            (isinstance(waypoints, (list, tuple)) and len(waypoints) > 0 and np.ndim(waypoints[0]) == 1)
-        lists = [np.asarray(waypoints, dtype=np.float64)] * self.B if shared else \
+        npos, cols = self.npos, self.wp_cols
+        yaw = self._headings(X)
+        lists = [np.asarray(waypoints, dtype=np.float64)] * self.B if _shared_list(waypoints) else \
             [np.asarray(w, dtype=np.float64) for w in waypoints]
         filt = []
         for i in range(self.B):
             wp = lists[i]
+            if wp.shape[1] < npos:
+                raise ValueError(f"{self.model} waypoints need {npos} columns")
             if len(wp) >= 2:                                   # filter_waypoints
-                aug = np.vstack((X[i, :2], wp[:, :2]))
+                aug = np.vstack((X[i, :npos], wp[:, :npos]))
                 dist = np.linalg.norm(np.diff(aug, axis=0), axis=1)
                 mask = np.concatenate(([False], dist >= self.reached_threshold))
                 wp = aug[mask]
-            filt.append(np.asarray(wp, dtype=np.float64)[:, :2].reshape(-1, 2))
+            row = np.zeros((len(wp), cols))
+            row[:, :npos] = wp[:, :npos]
+            filt.append(row)
         W = max(1, max(len(w) for w in filt))
-        wps = np.zeros((self.B, W, 2))
+        wps = np.zeros((self.B, W, cols))
         n_wp = np.zeros(self.B, dtype=np.int32)
         idx = np.zeros(self.B, dtype=np.int32)
         sm = np.zeros(self.B, dtype=np.int32)
-        goal = np.zeros((self.B, 3))
+        goal = np.zeros((self.B, cols + 1))
         for i in range(self.B):
             w = filt[i]
             n_wp[i] = len(w)
@@ -198,23 +262,19 @@ class BatchedTrackingController:
             # update_goal with state machine 'idle' (tracking.py:517-535)
             g = None
             if len(w) > 0:
-                if np.linalg.norm(X[i, :2] - w[0]) < self.reached_threshold:
+                if np.linalg.norm(X[i, :2] - w[0, :2]) < self.reached_threshold:
                     idx[i] = 1
                 if idx[i] < len(w):
                     g = w[idx[i]]
             if g is not None:                                   # tracking.py:214-226
                 ang = math.atan2(g[1] - X[i, 1], g[0] - X[i, 0])
-                yaw = self.yaw[i] if self.integrator else X[i, 2]
-                in_fov = abs(_wrap(ang - yaw)) <= self.fov_angle / 2
-                if not in_fov:
-                    if self.robot_spec["exploration"]:
-                        sm[i] = _lib.SM_ROTATE
-                        goal[i] = [g[0], g[1], 1.0]
-                    else:
-                        sm[i] = _lib.SM_STOP
+                in_fov = yaw is None or abs(_wrap(ang - yaw[i])) <= self.fov_angle / 2
+                if in_fov or self.robot_spec["exploration"]:
+                    sm[i] = _lib.SM_TRACK if in_fov else _lib.SM_ROTATE
+                    goal[i, :cols] = g
+                    goal[i, cols] = 1.0
                 else:
-                    sm[i] = _lib.SM_TRACK
-                    goal[i] = [g[0], g[1], 1.0]
+                    sm[i] = _lib.SM_STOP
         self.waypoints = torch.tensor(wps, dtype=self.tdtype, device=self.device).contiguous()
         self.n_wp = torch.tensor(n_wp, dtype=torch.int32, device=self.device)
         self.current_goal_index = torch.tensor(idx, dtype=torch.int32, device=self.device)
@@ -224,19 +284,24 @@ class BatchedTrackingController:
         self.ret_step.fill_(-1)
 
     # -- params --------------------------------------------------------------------------------
-    def _params(self, n_steps):
+    def _tracking_params(self, n_steps, p=None):
+        """sc_tracking_params, as the fused 'cbf_qp' rollouts and the select / apply pair of the four-state models take it: the one
+        fill of that struct, into ``p`` where another struct embeds it."""
         rs = self.robot_spec
-        p = _lib.TrackingParams()
+        if p is None:
+            p = _lib.TrackingParams()
         p.qp = make_params(rs, self.cbf_param, self.dt, rs["radius"], self.io_dtype, _lib.DTYPE_F64)
         p.n_steps = int(n_steps)
         p.step_offset = int(self.steps_done)                     # ret_step is an absolute control-step index
-        p.max_waypoints = int(self.waypoints.shape[1])
+        p.max_waypoints = self.waypoints.shape[1]
         p.waypoints_shared = 0
         p.enable_rotation = 1 if self.enable_rotation else 0
         p.dyn_obs = 1 if self.dyn_obs else 0
         p.num_constraints = self.num_constraints
         p.reached_threshold = self.reached_threshold
         p.rotation_threshold = self.rotation_threshold
+        if not self._nominal_gains:
+            return p
         p.v_max = float(rs["v_max"])
         p.v_min = float(rs.get("v_min", 0.0))
         if self.model == "DoubleIntegrator2D":                  # double_integrator2D.py:117-118, :151
@@ -253,18 +318,21 @@ class BatchedTrackingController:
         p.wheel_base = float(rs.get("wheel_base", 0.0))
         return p
 
-    def _od_params(self, n_steps):
-        """sc_tracking_od_params: 'track' runs nominal_input(goal, k_omega=3.0, k_a=0.5, k_v=0.5) (tracking.py:601-602), which the
-        spec's nominal_k_* override for DynamicUnicycle2D only (dynamic_unicycle2D.py:84-86; the KinematicBicycle2D family takes the
-        forwarded gains as they are, robots/robot.py:406-407); stop() brakes with nominal_k_a or 1.0 (dynamic_unicycle2D.py:106-108)."""
+    def _od_params(self, n_steps, p=None):
+        """sc_tracking_od_params (into ``p`` where sc_tracking_quad2d_params embeds it): 'track' runs nominal_input(goal, k_omega=3.0,
+        k_a=0.5, k_v=0.5) (tracking.py:601-602), which the spec's nominal_k_* override for DynamicUnicycle2D only
+        (dynamic_unicycle2D.py:84-86; the KinematicBicycle2D family takes the forwarded gains as they are, robots/robot.py:406-407);
+        stop() brakes with nominal_k_a or 1.0 (dynamic_unicycle2D.py:106-108).  A class without ``_nominal_gains`` leaves the four zero."""
         rs = self.robot_spec
-        p = _lib.TrackingOdParams()
-        p.track = self._params(n_steps)
-        du = self.model == "DynamicUnicycle2D"
-        p.track.k_omega = float(rs.get("nominal_k_omega", 3.0)) if du else 3.0
-        p.track.k_a = float(rs.get("nominal_k_a", 0.5)) if du else 0.5
-        p.track.k_v = float(rs.get("nominal_k_v", 0.5)) if du else 0.5
-        p.k_a_stop = float(rs.get("nominal_k_a", 1.0)) if du else 1.0
+        if p is None:
+            p = _lib.TrackingOdParams()
+        t = self._tracking_params(n_steps, p.track)
+        if self._nominal_gains:
+            du = self.model == "DynamicUnicycle2D"
+            t.k_omega = float(rs.get("nominal_k_omega", 3.0)) if du else 3.0
+            t.k_a = float(rs.get("nominal_k_a", 0.5)) if du else 0.5
+            t.k_v = float(rs.get("nominal_k_v", 0.5)) if du else 0.5
+            p.k_a_stop = float(rs.get("nominal_k_a", 1.0)) if du else 1.0
         p.omega_ref[0] = float(self.cbf_param.get("omega1", 1.0))
         p.omega_ref[1] = float(self.cbf_param.get("omega2", 1.0))
         p.p_sb[0] = float(self.cbf_param.get("p_sb1", 1e4))
@@ -272,125 +340,120 @@ class BatchedTrackingController:
         return p
 
     # -- stepping -------------------------------------------------------------------------------
+    def _record_buffers(self, n, more=()):
+        """``[traj_X [n,B,nx], traj_U [n,B,nu]]`` and one ``[n,B,*shape]`` buffer per ``(shape, dtype)`` of ``more``."""
+        torch = self.torch
+        new = lambda shape, dtype: torch.empty((n, self.B) + shape, dtype=getattr(torch, dtype) if dtype else self.tdtype, device=self.device)
+        return [new((self.nx,), None), new((self.nu,), None)] + [new(*m) for m in more]
+
+    def _rollout(self, fn, params, n, record, sensing=(), after=(), more=()):
+        """One launch of the fused rollout ``fn``.  Every rollout takes its parameter structs, the loop's state, the obstacle table,
+        ``u_pos``, the return codes and the record buffers traj_X / traj_U; the pointers of ``sensing`` go in after the table, those of
+        ``after`` behind traj_U, then one record buffer per entry of ``more`` (TRAJ_*).  Returns ``ret``, or ``(ret, traj_X, traj_U,
+        *more buffers)`` when ``record``."""
+        if record:
+            bufs = self._record_buffers(n, more)
+            traj = tuple(b.data_ptr() for b in bufs)
+            traj = traj[:2] + after + traj[2:]
+        else:
+            traj = (None, None) + after + (None,) * len(more)
+        M = self.obs.shape[0]
+        # one tuple and one unpacking: every argument behind a ``*`` in the call itself costs an instruction of its own
+        rc = fn(*(params + (self.B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(),
+                            self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(),
+                            self.obs.data_ptr() if M else None) + sensing
+                  + (self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr()) + traj
+                  + (self.torch.cuda.current_stream(self.device).cuda_stream,)))
+        if rc:
+            _lib.check(rc, fn.__name__)
+        self.steps_done += n
+        return (self.ret, *bufs) if record else self.ret
+
     def control_step(self, n=1, record=False):
         """Advance ``n`` control steps in one launch.  Returns ``ret`` [B] (and ``(traj_X [n,B,4],
         traj_U [n,B,2])`` when ``record``)."""
-        torch = self.torch
         if self.waypoints is None:
             raise RuntimeError("call set_waypoints first")
         if self.mpc is not None:
             return self._control_step_split(n, record)
         if self.od_qp:
             return self._control_step_od(n, record)
-        p = self._params(n)
-        tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
-        tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._lib.sc_tracking_rollout_batch(
-            C.byref(p), self.B, int(self.obs.shape[0]), self.X.data_ptr(), self.waypoints.data_ptr(),
-            self.n_wp.data_ptr(), self.current_goal_index.data_ptr(), self.state_machine.data_ptr(),
-            self.goal.data_ptr(), self.obs.data_ptr() if self.obs.shape[0] else None, self.u_pos.data_ptr(),
-            self.ret.data_ptr(), self.ret_step.data_ptr(),
-            tX.data_ptr() if record else None, tU.data_ptr() if record else None, stream)
-        _lib.check(rc, "sc_tracking_rollout_batch")
-        self.steps_done += n
-        return (self.ret, tX, tU) if record else self.ret
+        return self._rollout(self._lib.sc_tracking_rollout_batch, (C.byref(self._tracking_params(n)),), n, record)
 
     def _control_step_od(self, n, record):
         """control_step under 'optimal_decay_cbf_qp': one launch of csrc/tracking_od.hip.  With ``record`` returns
         ``(ret, traj_X [n,B,4], traj_U [n,B,2], traj_omega [n,B,2])``; ``self.omega`` / ``self.min_h`` carry across launches."""
-        torch = self.torch
-        p = self._od_params(n)
-        tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
-        tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
-        tW = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._lib.sc_tracking_od_rollout_batch(
-            C.byref(p), self.B, int(self.obs.shape[0]), self.X.data_ptr(), self.waypoints.data_ptr(),
-            self.n_wp.data_ptr(), self.current_goal_index.data_ptr(), self.state_machine.data_ptr(),
-            self.goal.data_ptr(), self.obs.data_ptr() if self.obs.shape[0] else None, self.u_pos.data_ptr(),
-            self.ret.data_ptr(), self.ret_step.data_ptr(),
-            tX.data_ptr() if record else None, tU.data_ptr() if record else None,
-            self.omega.data_ptr(), self.min_h.data_ptr(), tW.data_ptr() if record else None, stream)
-        _lib.check(rc, "sc_tracking_od_rollout_batch")
-        self.steps_done += n
-        return (self.ret, tX, tU, tW) if record else self.ret
+        return self._rollout(self._lib.sc_tracking_od_rollout_batch, (C.byref(self._od_params(n)),), n, record,
+                             after=(self.omega.data_ptr(), self.min_h.data_ptr()), more=TRAJ_OMEGA)
 
-    def _dummy_rows(self, like):
-        """[1000, 1000, 0, 0, 0, 0, 0] rows (update_tvp's padding, mpc_cbf.py:360) in the shape of one obstacle selection."""
-        d = getattr(self, "_dummy_obs", None)
-        if d is None or d.shape != like.shape[1:] or d.dtype != like.dtype:
-            d = self.torch.zeros(like.shape[1:], dtype=like.dtype, device=like.device)
-            d[:, 0] = 1000.0; d[:, 1] = 1000.0
-            self._dummy_obs = d
-        return d.unsqueeze(0)
+    def _easy_problem(self):
+        """State and goal rows of a problem every MPC kernel solves in a few iterations (the slots of agents outside 'track'): a
+        short run to a goal 1 m ahead."""
+        if self.model == "SingleIntegrator2D":
+            return [0.0, 0.0], [1.0, 0.0]
+        return [0.0, 0.0, 0.0, 0.5], [1.0, 0.0]                # unicycles / bicycle: 0.5 m/s along x; DoubleIntegrator2D: 0.5 m/s along y
 
-    def _easy_problem(self, X, goal):
-        """State and goal rows of a problem every MPC kernel solves in a few iterations (the slots of agents outside 'track')."""
-        e = getattr(self, "_easy", None)
-        if e is None or e[0].shape[1] != X.shape[1] or e[0].dtype != X.dtype:
-            xe = self.torch.zeros((1, X.shape[1]), dtype=X.dtype, device=X.device)
-            ge = self.torch.zeros((1, goal.shape[1]), dtype=goal.dtype, device=goal.device)
-            ge[0, 0] = 1.0
-            if X.shape[1] == 4:
-                xe[0, 3] = 0.5                                     # unicycles / bicycle: 0.5 m/s along x; DoubleIntegrator2D: 0.5 m/s along y
-            self._easy = e = (xe, ge)
-        return e
+    def _split_params(self):
+        return self._tracking_params(1)
+
+    def _split_solver(self):
+        """The MPC object of this call's launches.  Kernel 13 serves superellipsoid rows for the two robots whose DT barrier has that
+        branch (csrc/mpc_du_ms_se.hip); other robots' scenes with such rows run on the condensed kernels as before."""
+        ms = self.mpc_ms
+        if ms is None:
+            return self.mpc
+        se_ok = self.model in ("DynamicUnicycle2D", "DoubleIntegrator2D")
+        ms.superellipsoids = bool(self.obs_has_superellipsoid and se_ok)
+        return ms if (not self.obs_has_superellipsoid or se_ok) else self.mpc
 
     def _control_step_split(self, n, record):
         """control_step with an MPC position controller: per step  select (tracking.py:569-609) -> one MPC launch for
         the whole batch -> apply (tracking.py:627-668).  Agents whose state machine is not 'track' get u_ref
-        (mpc_cbf.py:379-381) and keep their u_prev; MPC failures are not reported to the loop (mpc_cbf.py:10)."""
+        (mpc_cbf.py:379-381) and keep their u_prev; MPC failures are not reported to the loop (mpc_cbf.py:10): a caller that
+        wants to know about unconverged steps reads ``mpc_status`` / ``mpc_iters`` (SC_STATUS_*, of every agent's last solve)."""
         torch = self.torch
-        p = self._params(1)
-        M, K, B = int(self.obs.shape[0]), self.num_constraints, self.B
-        obs_sel = torch.empty((B, K, 7), dtype=self.tdtype, device=self.device)
-        goal2 = torch.empty((B, 2), dtype=self.tdtype, device=self.device)
-        u_ref = torch.empty((B, 2), dtype=self.tdtype, device=self.device)
+        p = self._split_params()
+        M, B = int(self.obs.shape[0]), self.B
+        obs_sel = torch.empty((B, self.num_constraints, 7), dtype=self.tdtype, device=self.device)
+        goal_c = torch.empty((B, self.ng), dtype=self.tdtype, device=self.device)
+        u_ref = torch.empty((B, self.nu), dtype=self.tdtype, device=self.device)
         track = torch.empty(B, dtype=torch.int32, device=self.device)
-        tX = torch.empty((n, B, 4), dtype=self.tdtype, device=self.device) if record else None
-        tU = torch.empty((n, B, 2), dtype=self.tdtype, device=self.device) if record else None
+        tX, tU = self._record_buffers(n) if record else (None, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         obs_ptr = self.obs.data_ptr() if M else None
+        select, apply, apply_extra = getattr(self._lib, self._SPLIT[0]), getattr(self._lib, self._SPLIT[1]), self._SPLIT[2]
+        mpc = self._split_solver()
+        i_st, i_it = (2, 3) if self.pos_controller_type == "optimal_decay_mpc_cbf" else (1, 2)     # after u (and the decay multipliers)
+        xy_only = self.model == "SingleIntegrator2D"           # csrc/mpc_lin.hip takes its two states
+        (xe, ge), u_zero, dummy = self._easy, self._u_zero, self._dummy_obs
         for k in range(n):
-            rc = self._lib.sc_tracking_select_batch(
+            rc = select(
                 C.byref(p), B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(),
                 self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
-                self.ret.data_ptr(), obs_sel.data_ptr(), goal2.data_ptr(), u_ref.data_ptr(), track.data_ptr(), stream)
-            _lib.check(rc, "sc_tracking_select_batch")
-            Xm = self.X[:, :2].contiguous() if self.model == "SingleIntegrator2D" else self.X
-            # OptimalDecayMPCCBF has five fixed obstacle slots (optimal_decay_mpc_cbf.py:249-252,333-339: padded_obs[:5]):
-            # it sees the five nearest of the selected rows, MPCCBF all num_constraints of them
-            obs_in = obs_sel[:, :5].contiguous() if (self.pos_controller_type == "optimal_decay_mpc_cbf" and K > 5) else obs_sel
+                self.ret.data_ptr(), obs_sel.data_ptr(), goal_c.data_ptr(), u_ref.data_ptr(), track.data_ptr(), stream)
+            _lib.check(rc, self._SPLIT[0])
+            Xm = self.X[:, :2].contiguous() if xy_only else self.X
+            obs_in = obs_sel[:, :5].contiguous() if self._od_slots else obs_sel
             # Agents outside 'track' get u_ref and the reference does not solve for them (mpc_cbf.py:379-381).  Their slots of the batched
-            # launch are handed ONE easy problem (_easy_problem: a short run to a goal 1 m ahead, dummy obstacle rows) instead of a solve
-            # whose result is discarded and which may run the whole iteration budget: an agent turning on the spot (v = 0) makes a
-            # degenerate NLP that crawled for up to 1700 iterations.  No host round trip: four selects on the device.
+            # launch are handed ONE easy problem (_easy_problem, dummy obstacle rows) instead of a solve whose result is discarded and
+            # which may run the whole iteration budget: an agent turning on the spot (v = 0) makes a degenerate NLP that crawled for up
+            # to 1700 iterations.  No host round trip: four selects on the device.
             tr = (track != 0).unsqueeze(1)
-            xe, ge = self._easy_problem(Xm, goal2)
             X_in = torch.where(tr, Xm, xe).contiguous()
-            goal_in = torch.where(tr, goal2, ge).contiguous()
-            up_in = torch.where(tr, self.u_prev, torch.zeros_like(self.u_prev)).contiguous()
-            obs_in = torch.where(tr.unsqueeze(2), obs_in, self._dummy_rows(obs_in)).contiguous()
-            # kernel 13 serves superellipsoid rows for the two robots whose DT barrier has that branch (csrc/mpc_du_ms_se.hip); other robots' scenes
-            # with such rows run on the condensed kernels as before
-            ms = getattr(self, "mpc_ms", None)
-            se_ok = self.model in ("DynamicUnicycle2D", "DoubleIntegrator2D")
-            if ms is not None:
-                ms.superellipsoids = bool(self.obs_has_superellipsoid and se_ok)
-            mpc = ms if (ms is not None and (not self.obs_has_superellipsoid or se_ok)) else self.mpc
+            goal_in = torch.where(tr, goal_c, ge).contiguous()
+            up_in = torch.where(tr, self.u_prev, u_zero).contiguous()
+            obs_in = torch.where(tr.unsqueeze(2), obs_in, dummy).contiguous()
             out = mpc.solve(X_in, up_in, goal_in, obs_in)
-            u_mpc, st = (out[0], out[2]) if self.pos_controller_type == "optimal_decay_mpc_cbf" else (out[0], out[1])
-            its = out[3] if self.pos_controller_type == "optimal_decay_mpc_cbf" else out[2]
-            self._raw_iters, self._raw_track = its, track                      # (what the launch ran, slots outside 'track' included)
+            u_mpc, st, its = out[0], out[i_st], out[i_it]
+            self._raw_iters, self._raw_track = its, track
             u = torch.where(tr, u_mpc, u_ref).contiguous()
             self.u_prev = torch.where(tr, u_mpc, self.u_prev).contiguous()
-            self.mpc_status = torch.where(track != 0, st, self.mpc_status)      # (see BatchedQuadTrackingController: status / iterations of the last solve)
-            self.mpc_iters = torch.where(track != 0, its, getattr(self, "mpc_iters", torch.zeros_like(its)))
-            rc = self._lib.sc_tracking_apply_batch(
+            self.mpc_status = torch.where(track != 0, st, self.mpc_status)
+            self.mpc_iters = torch.where(track != 0, its, self.mpc_iters)
+            rc = apply(
                 C.byref(p), B, M, self.steps_done + k, self.X.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
-                u.data_ptr(), None, self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), stream)
-            _lib.check(rc, "sc_tracking_apply_batch")
+                u.data_ptr(), *apply_extra, self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), stream)
+            _lib.check(rc, self._SPLIT[1])
             if record:
                 tX[k] = self.X
                 tU[k] = self.u_pos
@@ -424,45 +487,37 @@ class BatchedQuadTrackingController(BatchedTrackingController):
     [x, z(, .)] or six states; Quad3D: [x, y], [x, y, yaw], [x, y, z, yaw] or twelve states); waypoints are [x, y, z] rows for
     Quad3D (the example's third column -- a heading for the planar models -- is the altitude goal there, tracking.py:501-502)."""
 
+    _SPLIT = ("sc_quadtrack_select_batch", "sc_quadtrack_apply_batch", ())
+    # Quad2D's nominal input runs at its own gains under both fused controllers (robots/robot.py:410-413 drops the k_omega / k_a / k_v
+    # that tracking.py:602 passes) and reads no speed bound
+    _nominal_gains = False
+
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, dyn_obs=False,
                  io_dtype="f64", device="cuda:0"):
-        import torch
-        self.torch = torch
         controller_type = controller_type or {"pos": "mpc_cbf"}
         self.pos_controller_type = controller_type.get("pos", "mpc_cbf")
-        self.model = robot_spec["model"]
+        model = robot_spec["model"]
         self.qp_ctrl = self.pos_controller_type in QUAD2D_QP_CONTROLLERS
         self.od_qp = self.pos_controller_type == "optimal_decay_cbf_qp"
-        if self.qp_ctrl and self.model != "Quad2D":
-            raise ValueError(f"{self.model} closed loop: position controller 'mpc_cbf' (the reference has no CBF-QP barrier for it)")
+        if self.qp_ctrl and model != "Quad2D":
+            raise ValueError(f"{model} closed loop: position controller 'mpc_cbf' (the reference has no CBF-QP barrier for it)")
         if self.pos_controller_type != "mpc_cbf" and not self.qp_ctrl:
             raise ValueError("Quad2D closed loop: position controllers 'mpc_cbf' (the reference's default), 'cbf_qp', "
                              "'optimal_decay_cbf_qp'; Quad3D / VTOL2D: 'mpc_cbf'")
         if dyn_obs and not self.qp_ctrl:
             raise ValueError("moving obstacle tables are stepped by the fused 'cbf_qp' / 'optimal_decay_cbf_qp' rollouts only")
-        self.q3 = self.model == "Quad3D"
-        self.vt = self.model == "VTOL2D"
-        self.robot_spec = complete_robot_spec(robot_spec)
-        self.robot_spec.setdefault("exploration", False)
-        self.integrator = False
-        self.dt, self.enable_rotation, self.dyn_obs = float(dt), bool(enable_rotation), bool(dyn_obs)
-        self.device = torch.device(device)
-        self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]
-        self.tdtype = torch.float32 if io_dtype == "f32" else torch.float64
-        self.num_constraints = int(self.robot_spec.get("num_constraints", 10))
+        self.q3 = model == "Quad3D"
+        self.vt = model == "VTOL2D"
+        self._configure(robot_spec, dt, enable_rotation, dyn_obs, io_dtype, device)
         if self.qp_ctrl and not self.od_qp and not 1 <= self.num_constraints <= _lib.TRACKING_MAX_CONSTRAINTS:
             raise ValueError(f"num_constraints must be in [1, {_lib.TRACKING_MAX_CONSTRAINTS}]")
-        self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))
-        self.rotation_threshold = 0.1
-        self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))
-        self._lib = _lib.load()
         self.nx, self.nu, self.ng = (12, 4, 3) if self.q3 else ((6, 4, 2) if self.vt else (6, 2, 2))
-        self._pos_cols = [0, 1, 2] if self.q3 else [0, 1]                  # position entries of a state row (Quad3D: x, y, z; planar: x, z)
+        self.npos = 3 if self.q3 else 2                        # position entries of a state row (Quad3D: x, y, z; planar: x, z)
+        self.wp_cols = 2 if self.qp_ctrl else 3                # the fused rollouts take planar rows: [B,W,2] and (gx, gz, valid)
         X0 = np.asarray(X0, dtype=np.float64)
         if X0.ndim == 1:
             X0 = X0[None, :]
-        B = X0.shape[0]
-        X = np.zeros((B, self.nx))
+        X = np.zeros((X0.shape[0], self.nx))
         if self.vt:                                            # tracking.py:94-99
             if X0.shape[1] in (2, 3):
                 X[:, :2] = X0[:, :2]
@@ -489,27 +544,8 @@ class BatchedQuadTrackingController(BatchedTrackingController):
                 X = X0.copy()
             else:
                 raise ValueError("Invalid initial state dimension for Quad3D")
-        self.B = B
-        t = lambda a, dt_=None: torch.tensor(a, dtype=dt_ or self.tdtype, device=self.device)
-        self.X = t(X)
-        self.state_machine = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.current_goal_index = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.goal = torch.zeros((B, 3 if self.qp_ctrl else 4), dtype=self.tdtype, device=self.device)   # gx, gy, (gz,) valid
-        self.ret = torch.zeros(B, dtype=torch.int32, device=self.device)
-        self.ret_step = torch.full((B,), -1, dtype=torch.int32, device=self.device)
-        self.u_pos = torch.zeros((B, self.nu), dtype=self.tdtype, device=self.device)
-        self.set_obstacles(obs)
-        self.waypoints = self.n_wp = None
-        self.steps_done = 0
-        self.mpc = None
+        self._allocate(X, obs, cbf_qp=self.qp_ctrl)
         if self.qp_ctrl:                                       # the fused rollout of csrc/tracking_quad_qp.hip: no MPC object
-            if self.od_qp:
-                self.cbf_param = apply_od_overrides(default_od_param(self.model), self.robot_spec)
-                ref = [float(self.cbf_param.get("omega1", 1.0)), float(self.cbf_param.get("omega2", 1.0))]
-                self.omega = torch.tensor([ref] * B, dtype=self.tdtype, device=self.device).contiguous()
-                self.min_h = torch.full((B,), float("inf"), dtype=self.tdtype, device=self.device)
-            else:
-                self.cbf_param = apply_cbf_overrides(default_cbf_param(self.model), self.robot_spec)
             return
         if self.q3:
             from .position_control.mpc_cbf_linear import BatchedLinearMPCCBF as cls
@@ -526,9 +562,7 @@ class BatchedQuadTrackingController(BatchedTrackingController):
         # 3000), and ONE hard NLP of the batch then holds a control step for as long as its solve takes (measured on 256 VTOL2D aircraft
         # flying the example scene at once: 0.3 s per step while a few of them face an infeasible approach, 7 ms afterwards)
         kw = {"max_iter": int(self.robot_spec["mpc_max_iter"])} if "mpc_max_iter" in self.robot_spec else {}
-        self.mpc = cls(self.robot_spec, dt=self.dt, io_dtype=io_dtype, **kw)
-        self.u_prev = torch.zeros((B, self.nu), dtype=self.tdtype, device=self.device)
-        self.mpc_status = torch.zeros(B, dtype=torch.int32, device=self.device)
+        self._init_split(cls(self.robot_spec, dt=self.dt, io_dtype=io_dtype, **kw))
 
     def set_obstacles(self, obs):
         super().set_obstacles(obs)
@@ -537,107 +571,30 @@ class BatchedQuadTrackingController(BatchedTrackingController):
             raise ValueError("Quad2D under 'cbf_qp' / 'optimal_decay_cbf_qp': the obstacle table holds a superellipsoid row "
                              "(column 6 >= 0.5), for which Quad2D has no barrier")
 
-    def set_waypoints(self, waypoints):
-        """set_waypoints / filter_waypoints / first update_goal (tracking.py:197-262, 497-535) on the host."""
-        torch = self.torch
-        X = self.X.double().cpu().numpy()
-        npos = 3 if self.q3 else 2
-        shared = (isinstance(waypoints, np.ndarray) and waypoints.ndim == 2) or \
-            (isinstance(waypoints, (list, tuple)) and len(waypoints) > 0 and np.ndim(waypoints[0]) == 1)
-        lists = [np.asarray(waypoints, dtype=np.float64)] * self.B if shared else [np.asarray(w, dtype=np.float64) for w in waypoints]
-        filt = []
-        for i in range(self.B):
-            wp = lists[i]
-            if wp.shape[1] < npos:
-                raise ValueError(f"{self.model} waypoints need {npos} columns")
-            if len(wp) >= 2:
-                aug = np.vstack((X[i, :npos], wp[:, :npos]))
-                dist = np.linalg.norm(np.diff(aug, axis=0), axis=1)
-                wp = aug[np.concatenate(([False], dist >= self.reached_threshold))]
-            w3 = np.zeros((len(wp), 3))
-            w3[:, :npos] = np.asarray(wp, dtype=np.float64)[:, :npos]
-            filt.append(w3)
-        W = max(1, max(len(w) for w in filt))
-        wps = np.zeros((self.B, W, 3)); n_wp = np.zeros(self.B, dtype=np.int32); idx = np.zeros(self.B, dtype=np.int32)
-        sm = np.zeros(self.B, dtype=np.int32); goal = np.zeros((self.B, 4))
-        for i in range(self.B):
-            w = filt[i]
-            n_wp[i] = len(w)
-            wps[i, : len(w)] = w
-            g = None
-            if len(w) > 0:
-                if np.linalg.norm(X[i, :2] - w[0, :2]) < self.reached_threshold:
-                    idx[i] = 1
-                if idx[i] < len(w):
-                    g = w[idx[i]]
-            if g is not None:
-                ang = math.atan2(g[1] - X[i, 1], g[0] - X[i, 0])
-                # is_in_fov (robots/robot.py:854-872): always True for Quad2D; yaw = X[5] for Quad3D (robot.py:451-452)
-                in_fov = (not self.q3) or abs(_wrap(ang - X[i, 5])) <= self.fov_angle / 2
-                if not in_fov:
-                    if self.robot_spec["exploration"]:
-                        sm[i] = _lib.SM_ROTATE
-                        goal[i] = [g[0], g[1], g[2], 1.0]
-                    else:
-                        sm[i] = _lib.SM_STOP
-                else:
-                    sm[i] = _lib.SM_TRACK
-                    goal[i] = [g[0], g[1], g[2], 1.0]
-        self.waypoints = torch.tensor(wps, dtype=self.tdtype, device=self.device).contiguous()
-        self.n_wp = torch.tensor(n_wp, dtype=torch.int32, device=self.device)
-        self.current_goal_index = torch.tensor(idx, dtype=torch.int32, device=self.device)
-        self.state_machine = torch.tensor(sm, dtype=torch.int32, device=self.device)
-        self.goal = torch.tensor(goal, dtype=self.tdtype, device=self.device).contiguous()
-        if self.qp_ctrl:                                       # the fused rollout takes planar rows: [B,W,2] and (gx, gz, valid)
-            self.waypoints = self.waypoints[:, :, :2].contiguous()
-            self.goal = self.goal[:, [0, 1, 3]].contiguous()
-        self.ret.zero_()
-        self.ret_step.fill_(-1)
+    def _headings(self, X):
+        """is_in_fov (robots/robot.py:854-872): always True for Quad2D and VTOL2D; yaw = X[5] for Quad3D (robot.py:451-452)."""
+        return X[:, 5] if self.q3 else None
 
     def _qp_params(self, n_steps):
-        """sc_tracking_quad2d_params.  The nominal input runs at Quad2D's own gains under both controllers (robots/robot.py:410-413 drops
-        the k_omega / k_a / k_v that tracking.py:602 passes), so the gain fields stay zero."""
-        rs = self.robot_spec
+        """sc_tracking_quad2d_params: sc_tracking_od_params as Quad2D fills it (no gains), the controller and the inertia."""
         p = _lib.TrackingQuad2dParams()
-        t = p.od.track
-        t.qp = make_params(rs, self.cbf_param, self.dt, rs["radius"], self.io_dtype, _lib.DTYPE_F64)
-        t.n_steps, t.step_offset = int(n_steps), int(self.steps_done)
-        t.max_waypoints, t.waypoints_shared = int(self.waypoints.shape[1]), 0
-        t.enable_rotation = 1 if self.enable_rotation else 0
-        t.dyn_obs = 1 if self.dyn_obs else 0
-        t.num_constraints = self.num_constraints
-        t.reached_threshold, t.rotation_threshold = self.reached_threshold, self.rotation_threshold
-        p.od.omega_ref[0] = float(self.cbf_param.get("omega1", 1.0))
-        p.od.omega_ref[1] = float(self.cbf_param.get("omega2", 1.0))
-        p.od.p_sb[0] = float(self.cbf_param.get("p_sb1", 1e4))
-        p.od.p_sb[1] = float(self.cbf_param.get("p_sb2", 1e4))
+        self._od_params(n_steps, p.od)
         p.controller = _lib.QUAD2D_CTRL_OD_CBF_QP if self.od_qp else _lib.QUAD2D_CTRL_CBF_QP
-        p.inertia = float(rs["inertia"])
+        p.inertia = float(self.robot_spec["inertia"])
         return p
 
     def _control_step_qp(self, n, record):
         """control_step under 'cbf_qp' / 'optimal_decay_cbf_qp': one launch of csrc/tracking_quad_qp.hip.  With ``record`` returns
         ``(ret, traj_X [n,B,6], traj_U [n,B,2])`` and, under optimal decay, ``traj_omega [n,B,2]`` as a fourth entry."""
-        torch = self.torch
-        p = self._qp_params(n)
-        B, M = self.B, int(self.obs.shape[0])
-        new = lambda w: torch.empty((n, B, w), dtype=self.tdtype, device=self.device)
-        tX, tU = (new(6), new(2)) if record else (None, None)
-        tW = new(2) if (record and self.od_qp) else None
-        ptr = lambda a: a.data_ptr() if a is not None else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._lib.sc_tracking_quad2d_rollout_batch(
-            C.byref(p), B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(), self.current_goal_index.data_ptr(),
-            self.state_machine.data_ptr(), self.goal.data_ptr(), self.obs.data_ptr() if M else None, self.u_pos.data_ptr(),
-            self.ret.data_ptr(), self.ret_step.data_ptr(), ptr(tX), ptr(tU),
-            self.omega.data_ptr() if self.od_qp else None, self.min_h.data_ptr() if self.od_qp else None, ptr(tW), stream)
-        _lib.check(rc, "sc_tracking_quad2d_rollout_batch")
-        self.steps_done += n
-        if not record:
-            return self.ret
-        return (self.ret, tX, tU, tW) if self.od_qp else (self.ret, tX, tU)
+        p = (C.byref(self._qp_params(n)),)
+        if self.od_qp:
+            return self._rollout(self._lib.sc_tracking_quad2d_rollout_batch, p, n, record,
+                                 after=(self.omega.data_ptr(), self.min_h.data_ptr()), more=TRAJ_OMEGA)
+        # 'cbf_qp' has no decay multipliers: no omega, no min_h and no traj_omega
+        return self._rollout(self._lib.sc_tracking_quad2d_rollout_batch, p, n, record, after=(None, None, None))
 
-    def _params(self, n_steps=1):
+    def _quadtrack_params(self):
+        """sc_quadtrack_params of the select / apply pair (``_split_params`` of this class)."""
         rs = self.robot_spec
         p = _lib.QuadTrackParams()
         p.model = 1 if self.q3 else (2 if self.vt else 0)
@@ -660,67 +617,19 @@ class BatchedQuadTrackingController(BatchedTrackingController):
             p.inertia, p.f_min, p.f_max = float(rs["inertia"]), float(rs["f_min"]), float(rs["f_max"])
         return p
 
-    def _easy_problem(self, X, goal):
+    _split_params = _quadtrack_params
+
+    def _easy_problem(self):
         """The discarded slots' problem for the quadrotors (at rest, goal 1 m along x) and for VTOL2D (the cruise probe of
         tests/test_mpcvtol_gpu.py: 12 m/s at 10 m, goal 100 m ahead -- zero airspeed is a singular point of the aero model)."""
-        e = getattr(self, "_easy", None)
-        if e is None:
-            xe = self.torch.zeros((1, self.nx), dtype=X.dtype, device=X.device)
-            ge = self.torch.zeros((1, self.ng), dtype=goal.dtype, device=goal.device)
-            ge[0, 0] = 1.0
-            if self.vt:
-                xe[0, 1], xe[0, 3] = 10.0, 12.0
-                ge[0, 0], ge[0, 1] = 100.0, 10.0
-            self._easy = e = (xe, ge)
-        return e
+        if self.vt:
+            return [0.0, 10.0, 0.0, 12.0, 0.0, 0.0], [100.0, 10.0]
+        return [0.0] * self.nx, [1.0] + [0.0] * (self.ng - 1)
 
     def control_step(self, n=1, record=False):
-        torch = self.torch
         if self.waypoints is None:
             raise RuntimeError("call set_waypoints first")
-        if self.qp_ctrl:
-            return self._control_step_qp(n, record)
-        p = self._params()
-        M, K, B = int(self.obs.shape[0]), self.num_constraints, self.B
-        obs_sel = torch.empty((B, K, 7), dtype=self.tdtype, device=self.device)
-        goal_c = torch.empty((B, self.ng), dtype=self.tdtype, device=self.device)
-        u_ref = torch.empty((B, self.nu), dtype=self.tdtype, device=self.device)
-        track = torch.empty(B, dtype=torch.int32, device=self.device)
-        tX = torch.empty((n, B, self.nx), dtype=self.tdtype, device=self.device) if record else None
-        tU = torch.empty((n, B, self.nu), dtype=self.tdtype, device=self.device) if record else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        obs_ptr = self.obs.data_ptr() if M else None
-        for k in range(n):
-            rc = self._lib.sc_quadtrack_select_batch(
-                C.byref(p), B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(), self.current_goal_index.data_ptr(),
-                self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr, self.ret.data_ptr(), obs_sel.data_ptr(), goal_c.data_ptr(),
-                u_ref.data_ptr(), track.data_ptr(), stream)
-            _lib.check(rc, "sc_quadtrack_select_batch")
-            # (outside 'track' the slot gets a problem that is solved at once -- goal on the vehicle, dummy obstacle rows -- see
-            # BatchedTrackingController._control_step_split)
-            tr = (track != 0).unsqueeze(1)
-            xe, ge = self._easy_problem(self.X, goal_c)
-            X_in = torch.where(tr, self.X, xe).contiguous()
-            goal_in = torch.where(tr, goal_c, ge).contiguous()
-            up_in = torch.where(tr, self.u_prev, torch.zeros_like(self.u_prev)).contiguous()
-            obs_in = torch.where(tr.unsqueeze(2), obs_sel, self._dummy_rows(obs_sel)).contiguous()
-            out = self.mpc.solve(X_in, up_in, goal_in, obs_in)
-            u_mpc, st = out[0], out[1]
-            u = torch.where(tr, u_mpc, u_ref).contiguous()                       # mpc_cbf.py:379-381: u_ref passes through outside 'track'
-            self.u_prev = torch.where(tr, u_mpc, self.u_prev).contiguous()
-            # per-agent status / iteration count of the last MPC solve: the reference's `status` stays 'optimal' whatever IPOPT returned
-            # (mpc_cbf.py:10); a caller that wants to know about unconverged steps reads these (SC_STATUS_*)
-            self.mpc_status = torch.where(track != 0, st, self.mpc_status)
-            self.mpc_iters = torch.where(track != 0, out[2], getattr(self, "mpc_iters", torch.zeros_like(out[2])))
-            rc = self._lib.sc_quadtrack_apply_batch(
-                C.byref(p), B, M, self.steps_done + k, self.X.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
-                u.data_ptr(), self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), stream)
-            _lib.check(rc, "sc_quadtrack_apply_batch")
-            if record:
-                tX[k] = self.X
-                tU[k] = self.u_pos
-        self.steps_done += n
-        return (self.ret, tX, tU) if record else self.ret
+        return self._control_step_qp(n, record) if self.qp_ctrl else self._control_step_split(n, record)
 
 
 class BatchedSensingTrackingController(BatchedTrackingController):
@@ -833,13 +742,8 @@ class BatchedSensingTrackingController(BatchedTrackingController):
     def set_unknown_obs(self, rows):
         self._set_unknown_rows(self._normalise_unknown(rows))
 
-    def set_waypoints(self, waypoints):
-        yaw_t = self.yaw
-        self.yaw = yaw_t.double().cpu().numpy()                     # the base class reads the headings on the host
-        try:
-            super().set_waypoints(waypoints)
-        finally:
-            self.yaw = yaw_t
+    def _headings(self, X):
+        return self.yaw.double().cpu().numpy() if self.integrator else X[:, 2]
 
     def _sense_params(self):
         s = _lib.SenseParams()
@@ -853,22 +757,13 @@ class BatchedSensingTrackingController(BatchedTrackingController):
     def control_step(self, n=1, record=False):
         """Advance ``n`` control steps in one launch.  Returns ``ret`` [B], or ``(ret, traj_X [n,B,4], traj_U [n,B,2],
         traj_yaw [n,B], traj_seen [n,B] int64)`` when ``record``."""
-        torch = self.torch
         if self.waypoints is None:
             raise RuntimeError("call set_waypoints first")
-        p, s = self._params(n), self._sense_params()
-        mk = lambda shape, dt_=None: torch.empty(shape, dtype=dt_ or self.tdtype, device=self.device) if record else None
-        tX, tU, tYaw, tSeen = mk((n, self.B, 4)), mk((n, self.B, 2)), mk((n, self.B)), mk((n, self.B), torch.int64)
-        ptr = lambda a: a.data_ptr() if a is not None and a.numel() else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        rc = self._lib.sc_tracking_sense_rollout_batch(
-            C.byref(p), C.byref(s), self.B, int(self.obs.shape[0]), self.X.data_ptr(), self.waypoints.data_ptr(),
-            self.n_wp.data_ptr(), self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(),
-            ptr(self.obs), ptr(self.unknown_obs), self.seen.data_ptr(), self.yaw.data_ptr(), self.u_att.data_ptr(),
-            self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), ptr(tX), ptr(tU), ptr(tYaw), ptr(tSeen), stream)
-        _lib.check(rc, "sc_tracking_sense_rollout_batch")
-        self.steps_done += n
-        return (self.ret, tX, tU, tYaw, tSeen) if record else self.ret
+        p, s = self._tracking_params(n), self._sense_params()
+        unknown = self.unknown_obs.data_ptr() if self.unknown_obs.numel() else None
+        return self._rollout(self._lib.sc_tracking_sense_rollout_batch, (C.byref(p), C.byref(s)), n, record,
+                             sensing=(unknown, self.seen.data_ptr(), self.yaw.data_ptr(), self.u_att.data_ptr()),
+                             more=TRAJ_YAW_SEEN)
 
 
 class BatchedFleetTrackingController(BatchedTrackingController):
@@ -930,9 +825,7 @@ class BatchedFleetTrackingController(BatchedTrackingController):
 
     def set_waypoints(self, waypoints):
         """The whole fleet's waypoint lists (or one list shared by every agent); resets the return codes and records."""
-        shared = (isinstance(waypoints, np.ndarray) and waypoints.ndim == 2) or \
-            (isinstance(waypoints, (list, tuple)) and len(waypoints) > 0 and np.ndim(waypoints[0]) == 1)
-        if not shared:
+        if not _shared_list(waypoints):
             if len(waypoints) != self.n_agents:
                 raise ValueError(f"one waypoint list per agent of the fleet ({self.n_agents}) expected")
             waypoints = list(waypoints[self.lo:self.hi])
@@ -947,10 +840,9 @@ class BatchedFleetTrackingController(BatchedTrackingController):
         torch = self.torch
         if self.waypoints is None:
             raise RuntimeError("call set_waypoints first")
-        p = self._params(1)
+        p = self._tracking_params(1)
         M, K = int(self.obs.shape[0]), self.neighbours
-        tX = torch.empty((n, self.B, 4), dtype=self.tdtype, device=self.device) if record else None
-        tU = torch.empty((n, self.B, 2), dtype=self.tdtype, device=self.device) if record else None
+        tX, tU = self._record_buffers(n) if record else (None, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         obs_ptr = self.obs.data_ptr() if M else None
         for k in range(n):
