@@ -36,8 +36,10 @@ def get_nearest_unpassed_obs(model, all_obs, pos, yaw, obs_num):
     return cand[idx]
 
 
-def is_collide(X, obs_table, radius):
-    """Known-obstacle collision test, tracking.py:445-495 (circle and superellipsoid)."""
+def is_collide(X, obs_table, radius, note=None):
+    """Known-obstacle collision test, tracking.py:445-495 (circle and superellipsoid).  ``note(name, margin)``, when given, hears how
+    far each row tested was from deciding the other way (a NaN superellipsoid value never collides; under a non-integer exponent the
+    distance of either base from zero, where the value turns NaN, is reported as well)."""
     if obs_table is None:
         return False
     for o in np.atleast_2d(obs_table):
@@ -45,7 +47,10 @@ def is_collide(X, obs_table, radius):
             continue
         superell = o.shape[0] >= 7 and np.isclose(o[6], 1.0) and o[4] >= 2.0   # :428-443
         if not superell:
-            if math.hypot(X[0] - o[0], X[1] - o[1]) < o[2] + radius:
+            d = math.hypot(X[0] - o[0], X[1] - o[1])
+            if note is not None:
+                note("collision", abs(d - (o[2] + radius)))
+            if d < o[2] + radius:
                 return True
         else:
             ct, st = math.cos(o[5]), math.sin(o[5])
@@ -53,6 +58,10 @@ def is_collide(X, obs_table, radius):
             py = -st * (X[0] - o[0]) + ct * (X[1] - o[1])
             with np.errstate(all="ignore"):
                 h = np.float64(px / (o[2] + radius)) ** o[4] + np.float64(py / (o[3] + radius)) ** o[4] - 1
+            if note is not None and not np.isnan(h):
+                note("collision", abs(float(h)))
+            if note is not None and o[4] != round(o[4]):          # a base that changes sign turns the value into NaN
+                note("collision", min(abs(px / (o[2] + radius)), abs(py / (o[3] + radius))))
             if h <= 0:
                 return True
     return False
