@@ -3,6 +3,8 @@
 TEST INFRASTRUCTURE ONLY (see oracle/__init__.py).  Pinned on tests/golden/backup_cbf.npz, which
 tests/golden/make_golden_backup.py produced by running the reference's own code (rollout, sensitivities, rows, QP
 statement) -- only the QP minimiser comes from this repo's exact solver (OSQP is not installable; unique minimiser).
+backup_cbf_b.npz pins it the same way at a scenario whose parameters are pairwise different (tests/_evade_scenarios.py),
+so a parameter read from the wrong field shows.
 
 Follows, function by function:
   BackupCBF.solve_control_problem        position_control/backup_cbf_qp.py:563-794
@@ -69,8 +71,9 @@ def nominal_control(x, spec):
 
 
 def backup_control(x, env, spec):
-    """EvadeBackupController.compute_control (backup_controller.py:456-571), Kp = Kd = 2."""
-    Kp, Kd = 2.0, 2.0
+    """EvadeBackupController.compute_control (backup_controller.py:456-571); the gains are the instance's Kp / Kd (:449-450,
+    2.0 each unless the spec carries kp / kd)."""
+    Kp, Kd = spec.get("kp", 2.0), spec.get("kd", 2.0)
     px, py, vx, vy = x
     a_max = spec["a_max"]
     if env["goal_x_min"] <= px <= env["goal_x_max"] and -env["half_width"] <= py <= env["half_width"]:

@@ -97,16 +97,28 @@ class BatchedBackupCBF:
             raise ValueError("expected X[B,4], u_nom[B,2] or None, bullet_x[B] or [1]")
         return B, bullet_x.numel() == 1 and B != 1
 
-    def solve(self, X, u_nom, bullet_x, want_rows=False):
+    def solve(self, X, u_nom, bullet_x, want_rows=False, out=None):
+        """``out``: the output tensors to write, in the order they are returned (each with at least B leading entries,
+        entries past B are left alone); the first B entries of each are returned."""
         import torch
         B, shared = self._check(X, bullet_x, u_nom)
         dev = X.device
-        u = torch.empty((B, 2), dtype=self.torch_dtype, device=dev)
-        status = torch.empty((B,), dtype=torch.int32, device=dev)
-        using = torch.empty((B,), dtype=torch.int32, device=dev)
-        h_min = torch.empty((B,), dtype=self.torch_dtype, device=dev)
-        n_rows = torch.zeros((B,), dtype=torch.int32, device=dev) if want_rows else None
-        rows = torch.zeros((B, self.N, 3), dtype=torch.float64, device=dev) if want_rows else None
+        if out is not None:
+            u, status, using, h_min = out[:4]
+            n_rows, rows = (out[4], out[5]) if want_rows else (None, None)
+            want = [(u, self.torch_dtype, (2,)), (status, torch.int32, ()), (using, torch.int32, ()), (h_min, self.torch_dtype, ())]
+            if want_rows:
+                want += [(n_rows, torch.int32, ()), (rows, torch.float64, (self.N, 3))]
+            for t, dt_, tail in want:
+                if not (t.is_cuda and t.is_contiguous() and t.dtype == dt_ and t.shape[0] >= B and tuple(t.shape[1:]) == tail):
+                    raise ValueError("out: contiguous CUDA tensors u[>=B,2], status, using_backup, h_min[>=B] (n_rows[>=B], rows[>=B,N,3])")
+        else:
+            u = torch.empty((B, 2), dtype=self.torch_dtype, device=dev)
+            status = torch.empty((B,), dtype=torch.int32, device=dev)
+            using = torch.empty((B,), dtype=torch.int32, device=dev)
+            h_min = torch.empty((B,), dtype=self.torch_dtype, device=dev)
+            n_rows = torch.zeros((B,), dtype=torch.int32, device=dev) if want_rows else None
+            rows = torch.zeros((B, self.N, 3), dtype=torch.float64, device=dev) if want_rows else None
         p = make_params(self.env, self.robot_spec, self.dt, self.backup_horizon, self.io_dtype, bullet_shared=shared,
                         alpha=self.alpha, alpha_terminal=self.alpha_terminal, kp=self.kp, kd=self.kd)
         stream = torch.cuda.current_stream(dev).cuda_stream
@@ -115,7 +127,8 @@ class BatchedBackupCBF:
             status.data_ptr(), using.data_ptr(), h_min.data_ptr(), n_rows.data_ptr() if want_rows else None,
             rows.data_ptr() if want_rows else None, stream)
         _lib.check(rc, "sc_backupcbf_solve_batch")
-        return (u, status, using, h_min, n_rows, rows) if want_rows else (u, status, using, h_min)
+        res = (u, status, using, h_min, n_rows, rows) if want_rows else (u, status, using, h_min)
+        return tuple(t[:B] for t in res) if out is not None else res
 
     def rollout(self, X, bullet_x, ret, ret_step, n_ctrl, step_offset=0):
         """n_ctrl steps of the example's loop in one launch; X, bullet_x ([B]), ret, ret_step are updated in place.

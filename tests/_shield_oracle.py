@@ -14,6 +14,8 @@ box, and adds the wall test and the two bullet tests.  Every decision also repor
 |distance - threshold| over the comparisons that decided it (the collision tests of the chosen candidate and of the ones
 rejected before it; for MPS also |u - u_ref| against 1e-2), so a test can tell a true disagreement from a tie.
 """
+import json
+
 import numpy as np
 
 from oracle.backup_cbf import backup_control, bullet_hits, default_env, default_spec, di_step, nominal_control
@@ -232,11 +234,12 @@ def closed_loop(algo, x0=(20.0, 0.0, 0.0, 0.0), bullet_x0=-10.0, dt=0.1, backup_
     return out
 
 
-def replay(args):
+def replay(args, env=None, spec=None):
     """Warm-up steps of the example's loop from (x0, bullet_x0), then one more call: (u, info of that call, min margin over
     all calls, ret after the warm-up).  Top-level so a process pool can run it."""
     algo, x0, bx0, n_warm, dt, backup_horizon, nominal_horizon, event_offset = args
-    env, spec = default_env(), default_spec()
+    env = env or default_env()
+    spec = spec or default_spec()
     sh = Shield(algo, dt, backup_horizon, event_offset, env=env, spec=spec)
     M = int(nominal_horizon / dt)
     x, bx = np.asarray(x0, dtype=float).copy(), float(bx0)
@@ -269,10 +272,12 @@ def _replay_file(inp, outp):
     d = np.load(inp)
     algo, n_warm = int(d["algo"]), int(d["n_warm"])
     dt, bh, nh, eo = (float(v) for v in d["params"])
+    env = json.loads(str(d["env"])) if "env" in d.files else None
+    spec = json.loads(str(d["spec"])) if "spec" in d.files else None
     keys = ("u", "s", "idx", "clen", "net", "using_backup", "found", "margin", "ended")
     out = {k: [] for k in keys}
     for x0, bx0 in zip(d["X"], d["bx"]):
-        u, info, margin, ended = replay((algo, x0, bx0, n_warm, dt, bh, nh, eo))
+        u, info, margin, ended = replay((algo, x0, bx0, n_warm, dt, bh, nh, eo), env, spec)
         info = info or dict(s=-1, idx=-1, clen=-1, net=np.nan, using_backup=False, found=False)
         for k, v in (("u", u if u is not None else np.full(2, np.nan)), ("margin", margin), ("ended", ended)):
             out[k].append(v)
@@ -281,9 +286,9 @@ def _replay_file(inp, outp):
     np.savez(outp, **{k: np.array(v) for k, v in out.items()})
 
 
-def replay_many(algo, X0, bx0, n_warm, params=(0.1, 12.0, 10.0, 0.05), workers=MAX_WORKERS, timeout=900):
+def replay_many(algo, X0, bx0, n_warm, params=(0.1, 12.0, 10.0, 0.05), workers=MAX_WORKERS, timeout=900, env=None, spec=None):
     """replay() for every row, in at most MAX_WORKERS child processes; dict of arrays (u, s, idx, clen, net, using_backup,
-    found, margin, ended)."""
+    found, margin, ended).  env / spec as Shield and closed_loop take them (None: the example's)."""
     import os
     import subprocess
     import sys
@@ -294,10 +299,11 @@ def replay_many(algo, X0, bx0, n_warm, params=(0.1, 12.0, 10.0, 0.05), workers=M
         procs = []
         for j, idx in enumerate(parts):
             inp, outp = os.path.join(tmp, f"in{j}.npz"), os.path.join(tmp, f"out{j}.npz")
-            np.savez(inp, algo=algo, n_warm=n_warm, params=np.array(params, dtype=float), X=X0[idx], bx=bx0[idx])
-            env = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
+            scen = {k: json.dumps(v) for k, v in (("env", env), ("spec", spec)) if v is not None}
+            np.savez(inp, algo=algo, n_warm=n_warm, params=np.array(params, dtype=float), X=X0[idx], bx=bx0[idx], **scen)
+            penv = dict(os.environ, PYTHONPATH=os.pathsep.join([os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                                                                os.environ.get("PYTHONPATH", "")]))
-            procs.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), inp, outp], env=env), outp))
+            procs.append((subprocess.Popen([sys.executable, os.path.abspath(__file__), inp, outp], env=penv), outp))
         for p, _ in procs:
             if p.wait(timeout=timeout) != 0:
                 raise RuntimeError("shield oracle worker failed")

@@ -14,7 +14,11 @@ Writes tests/golden/shield.npz:
   loops    the example's closed loop (test_evade.py:434-497) for each algorithm and variant: state, bullet_x, u per step,
            is_using_backup(), actual_nominal_steps, current_time_idx, next_event_time, len(committed_u_traj) after the call,
            outcome (1 goal, -2 collision, 0 time-out) and the step it was reached at
-  calls    single calls from fresh shields at drawn (state, bullet) pairs: the same fields plus the committed trajectory."""
+  calls    single calls from fresh shields at drawn (state, bullet) pairs: the same fields plus the committed trajectory.
+
+and tests/golden/shield_b.npz, the same keys at scenario "B" of tests/_evade_scenarios.py (no two parameters equal): the
+same objects built the same way from B's numbers, the gains set on the EvadeBackupController instance; one loop (variant
+"base", LOOP_B) and 20 single calls per algorithm, plus the gains."""
 import os
 import sys
 
@@ -25,6 +29,9 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 
+sys.path.insert(0, os.path.dirname(HERE))
+
+import _evade_scenarios as SC  # noqa: E402
 import _ref_import  # noqa: E402
 
 _ref_import.install()
@@ -54,22 +61,34 @@ VARIANTS = {
     "dt005": (0.05, 12.0, 10.0, 0.05),
 }
 ALGOS = ("gatekeeper", "mps")
+# scenario B: its parameter set, and the start, bullet position and number of steps of its one loop per algorithm
+VARIANTS_B = {"base": (SC.DT["B"], SC.HORIZON["B"], 10.0, 0.05)}
+LOOP_B = ((22.0, 0.0, 0.0, 0.0), SC.ENV_KW["B"]["bullet_start_x"], 260)
 
 
-def build(algo, dt, backup_horizon, nominal_horizon, event_offset):
+def build(algo, dt, backup_horizon, nominal_horizon, event_offset, scenario="default"):
     cfg = EV.TestConfig(algo_type=algo)
     s = cfg.simulation
     s.dt, s.backup_horizon_time, s.nominal_horizon_time, s.event_offset = dt, backup_horizon, nominal_horizon, event_offset
     e = cfg.env
+    if scenario != "default":                                 # the example's configuration objects with the scenario's numbers
+        for k, v in SC.ENV_KW[scenario].items():
+            if hasattr(e, k):
+                setattr(e, k, v)
+        cfg.robot.radius, cfg.robot.a_max, cfg.robot.v_max = (SC.ROBOT[scenario][k] for k in ("radius", "a_max", "v_max"))
+        s.safety_margin = SC.ROBOT[scenario]["safety_margin"]
     env = EvadeEnv(hallway_length=e.hallway_length, hallway_width=e.hallway_width, pocket_x=e.pocket_x,
                    pocket_length=e.pocket_length, pocket_width=e.pocket_width, goal_length=e.goal_length,
-                   bullet_speed=e.bullet_speed, bullet_length=e.bullet_length, bullet_start_x=e.bullet_start_x)
+                   bullet_speed=e.bullet_speed, bullet_length=e.bullet_length, bullet_start_x=e.bullet_start_x,
+                   bullet_width=SC.ENV_KW[scenario]["bullet_width"])
     env._draw_bullet_bill = lambda: None                      # no figure
     spec = cfg.robot.to_dict()
     spec["safety_margin"] = s.safety_margin
     goal_bounds = {"x_min": env.goal_x_min, "x_max": env.goal_x_max, "y_min": -env.half_width, "y_max": env.half_width}
     nominal = EV.EvadeNominalController(spec)
     backup = EvadeBackupController(spec, dt, env.get_pocket_center(), env.get_pocket_bounds(), goal_bounds)
+    if scenario != "default":
+        backup.Kp, backup.Kd = SC.GAINS[scenario]["kp"], SC.GAINS[scenario]["kd"]
     dyn = DoubleIntegrator2D(dt, spec)
     if algo == "mps":                                         # test_evade.py:335-366
         sh = MPS(robot=dyn, robot_spec=spec, dt=dt, backup_horizon=backup_horizon, event_offset=event_offset, ax=None,
@@ -111,11 +130,14 @@ def record(sh):
                 net=float(sh.next_event_time), clen=int(len(sh.committed_u_traj)))
 
 
-def run_loop(algo, variant):
-    dt, bh, nh, eo = VARIANTS[variant]
-    cfg, env, sh, dyn, rollout_nominal = build(algo, dt, bh, nh, eo)
+def run_loop(algo, variant, scenario="default"):
+    dt, bh, nh, eo = (VARIANTS if scenario == "default" else VARIANTS_B)[variant]
+    cfg, env, sh, dyn, rollout_nominal = build(algo, dt, bh, nh, eo, scenario)
     state = np.array([cfg.simulation.initial_x, 0.0, 0.0, 0.0]).reshape(-1, 1)
     T = int(cfg.simulation.tf / dt)
+    if scenario != "default":
+        x0, env.bullet_x, T = LOOP_B
+        state = np.array(x0, dtype=float).reshape(-1, 1)
     rows = []
     outcome, out_step = 0, -1
     for step in range(T):                                     # test_evade.py:434-497
@@ -168,16 +190,16 @@ def draw(rng, kind):
     return x, bx
 
 
-def run_calls(algo, n, seed):
-    dt, bh, nh, eo = VARIANTS["base"]
+def run_calls(algo, n, seed, scenario="default"):
+    dt, bh, nh, eo = (VARIANTS if scenario == "default" else VARIANTS_B)["base"]
     rng = np.random.default_rng(seed)
     M = int(nh / dt)
     nb = int(bh / dt)
     L = M + 1 + nb
     rec = dict(X=[], bullet_x=[], U=[], using_backup=[], ans=[], idx=[], net=[], clen=[], cx=[], cu=[])
     for i in range(n):
-        x, bx = draw(rng, i % 5)
-        cfg, env, sh, dyn, rollout_nominal = build(algo, dt, bh, nh, eo)
+        x, bx = draw(rng, i % 5) if scenario == "default" else SC.draw_call_b(rng, i % 5)
+        cfg, env, sh, dyn, rollout_nominal = build(algo, dt, bh, nh, eo, scenario)
         env.bullet_x = float(bx)
         nom_x, nom_u = rollout_nominal(x.reshape(-1, 1), nh)
         sh.set_nominal_trajectory(nom_x, nom_u)
@@ -200,23 +222,28 @@ def run_calls(algo, n, seed):
     return out
 
 
-def gen():
+def gen(scenario="default"):
     out = {}
+    variants, n_calls, seeds, name = (VARIANTS, 30, (20261016, 20261017), "shield.npz") if scenario == "default" else (
+        VARIANTS_B, 20, (20261020, 20261021), "shield_b.npz")
     for algo in ALGOS:
-        for v in VARIANTS:
-            for k, a in run_loop(algo, v).items():
+        for v in variants:
+            for k, a in run_loop(algo, v, scenario).items():
                 out[f"loop_{algo}_{v}_{k}"] = a
-        for k, a in run_calls(algo, 30, 20261016 if algo == "gatekeeper" else 20261017).items():
+        for k, a in run_calls(algo, n_calls, seeds[0] if algo == "gatekeeper" else seeds[1], scenario).items():
             out[f"calls_{algo}_{k}"] = a
-    _, env, sh, _, _ = build("gatekeeper", *VARIANTS["base"])
+    _, env, sh, _, _ = build("gatekeeper", *variants["base"], scenario)
     out["env"] = np.array([env.hallway_length, env.half_width, env.pocket_x_min, env.pocket_x_max, env.pocket_y_min, env.pocket_y_max,
                            env.goal_x_min, env.goal_x_max, env.bullet_speed, env.bullet_length, env.bullet_width, env.bullet_start_x])
     out["spec"] = np.array([sh.robot_spec["radius"], sh.robot_spec["a_max"], sh.robot_spec["v_max"], sh.safety_margin,
                             sh.horizon_discount])
-    path = os.path.join(HERE, "shield.npz")
+    if scenario != "default":
+        out["gains"] = np.array([sh.backup_controller.Kp, sh.backup_controller.Kd])
+    path = os.path.join(HERE, name)
     np.savez_compressed(path, **out)
-    print("wrote shield.npz", os.path.getsize(path), "bytes")
+    print("wrote", name, os.path.getsize(path), "bytes")
 
 
 if __name__ == "__main__":
     gen()
+    gen("B")

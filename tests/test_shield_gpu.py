@@ -1,7 +1,8 @@
 """GPU: Gatekeeper / MPS kernels (csrc/shield.hip) through the C-ABI against the reference-executed fixtures
 (tests/golden/shield.npz) and the float64 oracle (tests/_shield_oracle.py).  The kernels repeat the reference's double
 operations without contraction, so decisions are identical and states agree to rounding; a decision whose oracle margin is
-within 1e-9 of a tie is counted, not compared."""
+within 1e-9 of a tie is counted, not compared.  The tests at the end repeat the fixture loop and the drawn batch at scenario B of
+tests/_evade_scenarios.py (tests/golden/shield_b.npz), where no two scenario parameters are equal."""
 import os
 
 import numpy as np
@@ -318,3 +319,92 @@ def test_argument_validation():
     ret = torch.zeros(4, dtype=torch.int32, device=DEV)
     with pytest.raises(ValueError):
         sh.rollout(X, bx[:1], st, ret, ret.clone(), 1)
+
+
+# ---- scenario B (tests/_evade_scenarios.py): no two parameters equal, so a wrong field in shield.hip, evade.hpp or the parameter
+# fill of BatchedShield shows ------------------------------------------------------------------------------------------------
+import _evade_scenarios as SC  # noqa: E402
+
+GB = np.load(os.path.join(os.path.dirname(__file__), "golden", "shield_b.npz"))
+
+
+def shield_b(algo):
+    dt, bh, nh, eo = (float(v) for v in GB[f"loop_{algo}_base_params"])
+    rb = SC.ROBOT["B"]
+    return sca.BatchedShield(algo, robot_spec={k: rb[k] for k in ("radius", "a_max", "v_max")}, env=SC.kernel_env("B"), dt=dt,
+                             backup_horizon=bh, nominal_horizon=nh, event_offset=eo, safety_margin=rb["safety_margin"],
+                             kp=SC.GAINS["B"]["kp"], kd=SC.GAINS["B"]["kd"])
+
+
+@pytest.mark.parametrize("algo", list(ALGOS))
+def test_scenario_b_fixture_loop_as_agent_0(algo):
+    k = f"loop_{algo}_base_"
+    sh = shield_b(algo)
+    B = 256
+    X0, bx0 = SC.draw_calls_b(B, seed=5)
+    X0[0], bx0[0] = GB[k + "X"][0], GB[k + "bullet_x"][0]
+    T = n = len(GB[k + "X"])
+    X, bx, st = t(X0), t(bx0), sh.new_state(B, DEV)
+    ret = torch.zeros(B, dtype=torch.int32, device=DEV)
+    rs = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    nb = torch.zeros(B, dtype=torch.int32, device=DEV)
+    f = sh.fields(st, B)
+    rec = []
+    for step in range(T):
+        x_pre, b_pre = X[0].clone(), bx[:1].clone()
+        u, using = sh.rollout(X, bx, st, ret, rs, 1, step_offset=step, backup_steps=nb)
+        rec.append(torch.cat([x_pre, u[0], torch.stack([using[0], f["s"][0], f["idx"][0], f["clen"][0]]).double(), f["net"][:1], b_pre]))
+    R = torch.stack(rec).cpu().numpy()
+    assert (int(ret[0]), int(rs[0])) == (int(GB[k + "outcome"]), int(GB[k + "outcome_step"]))
+    assert np.abs(R[:n, 0:4] - GB[k + "X"]).max() <= 1e-9
+    assert np.abs(R[:n, 4:6] - GB[k + "U"]).max() <= 1e-9
+    for j, g in ((6, "using_backup"), (7, "ans"), (8, "idx"), (9, "clen")):
+        assert np.array_equal(R[:n, j].astype(np.int64), GB[k + g].astype(np.int64)), g
+    assert np.abs(R[:n, 10] - GB[k + "net"]).max() <= 1e-12
+    assert np.abs(R[:n, 11] - GB[k + "bullet_x"]).max() <= 1e-9
+    assert int(nb[0]) == int(GB[k + "using_backup"].sum())
+    X2, bx2, st2 = t(X0), t(bx0), sh.new_state(B, DEV)
+    ret2 = torch.zeros(B, dtype=torch.int32, device=DEV)
+    rs2 = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    nb2 = torch.zeros(B, dtype=torch.int32, device=DEV)
+    sh.rollout(X2, bx2, st2, ret2, rs2, T, backup_steps=nb2)
+    for a, b in ((X, X2), (bx, bx2), (st, st2), (ret, ret2), (rs, rs2), (nb, nb2)):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("algo", list(ALGOS))
+def test_scenario_b_drawn_batch_against_oracle(algo):
+    """test_drawn_batch_against_oracle at scenario B: 1024 situations, four warm-up steps, one call; 256 replayed by the oracle."""
+    B, W = 1024, 4
+    X0, bx0 = SC.draw_calls_b(B, seed=11 + ALGOS[algo])
+    sh = shield_b(algo)
+    X, bx, st = t(X0), t(bx0), sh.new_state(B, DEV)
+    ret = torch.zeros(B, dtype=torch.int32, device=DEV)
+    rs = torch.full((B,), -1, dtype=torch.int32, device=DEV)
+    sh.rollout(X, bx, st, ret, rs, W)
+    u, using, s = sh.step(X, bx, st)
+    f = sh.fields(st, B)
+    u, using, s, idx, clen, net, ret = (a.cpu().numpy() for a in (u, using, s, f["idx"], f["clen"], f["net"], ret))
+    sub = np.arange(0, B, 4)
+    o = SO.replay_many(ALGOS[algo], X0[sub], bx0[sub], W, params=tuple(float(v) for v in GB[f"loop_{algo}_base_params"]),
+                       env=SC.oracle_env(), spec=SC.oracle_spec())
+    ties = compared = 0
+    kinds = set()
+    for j, i in enumerate(sub):
+        assert bool(ret[i]) == bool(o["ended"][j]), i
+        if o["ended"][j]:
+            continue
+        if o["margin"][j] <= 1e-9:
+            ties += 1
+            continue
+        compared += 1
+        assert (s[i], idx[i], clen[i], bool(using[i])) == (o["s"][j], o["idx"][j], o["clen"][j], bool(o["using_backup"][j])), i
+        assert abs(net[i] - o["net"][j]) <= 1e-12
+        assert np.abs(u[i] - o["u"][j]).max() <= 1e-12, (i, u[i], o["u"][j])
+        kinds.add((bool(o["s"][j] > 0), bool(o["found"][j]), bool(o["using_backup"][j])))
+    print(f"{algo}: compared {compared}, ties {ties} of {len(sub)}")
+    # The warm-up ends the agents drawn inside the goal zone (half of the one kind in five drawn around its edge, 10 %) and those
+    # the bullet reaches within four steps (nose gaps below ~1.7 m among the two kinds drawn with the bullet close behind, ~5 %).
+    assert compared >= 0.8 * len(sub)
+    assert ties <= 0.005 * len(sub)
+    assert len(kinds) >= 3
