@@ -14,6 +14,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
 #include <utility>
 
 #include <cstdlib>
@@ -370,22 +371,35 @@ struct Coop8Consts {
     sc_d8 t0;                                              // SinCosTab: two_over_pi, pio2_1, pio2_2, pio2_3, s[0..3]
     sc_d8 t1;                                              //            s[4], s[5], c[0..5]
     sc_d8 k0;                                              // R, g1, g2, inv_dt, inv_dt2, lo0, hi0, lo1
-    sc_d8 k1;                                              // hi1, BoxTol: lo0, hi0, lo1, hi1; three spare
-    int hard;
+    sc_d8 k1;                                              // hi1, BoxTol: lo0, hi0, lo1, hi1; SolveLit: tol_feas, eps_par, +inf
     unsigned B;                                            // read by the !FULL instantiations only
 };
 
 // normalise_row with the sum of squares written as the fused form the generic kernel compiles to.  `n0 * n0 + n1 * n1` leaves it to
 // the compiler which product stays a rounded multiply and which goes into the FMA; behind the generic kernel's `used` selects it
 // picks fma(n1, n1, n0 * n0), without them (here) the other one, and the two differ in the last bit of some rows.
+// The guard `nn > 0 ? rsqrt_(nn) : 1` is off the path of an ordinary wave: the reciprocal square root is taken of every lane with the
+// whole wave enabled (v_rsq_f64 of 0, a negative or a NaN traps nothing), and only a wave in which some row has not nn > 0
+// (all-zero, underflowed, NaN) runs the select, which puts 1.0 where it is today.  Every lane gets the bits it got.
 __device__ __forceinline__ void normalise_row_as_generic(double& n0, double& n1, double& c, double& poison) {
     const double nn = __builtin_fma(n1, n1, n0 * n0);
     poison += 0.0 * (nn + c);
-    const double inv = nn > 0.0 ? rsqrt_(nn) : 1.0;
+    double inv = rsqrt_(nn);
+    if (__builtin_amdgcn_ballot_w64(!(nn > 0.0)) != 0ull) {                   // wave-uniform, cold
+        asm volatile("");
+        inv = nn > 0.0 ? inv : 1.0;
+    }
     n0 *= inv; n1 *= inv; c *= inv;
 }
 
-template <typename TIO, bool FULL, bool HAS_H>
+// base + off bytes, off a 32-bit lane value: the scalar-base form of the global loads and stores (no 64-bit address arithmetic)
+template <typename T>
+__device__ __forceinline__ T* at_byte(T* base, unsigned off) {
+    using C = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+    return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + off);
+}
+
+template <typename TIO, bool FULL, bool HAS_H, bool HARD>
 __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
                                                             const TIO* __restrict__ u_ref, TIO* __restrict__ u_out,
                                                             TIO* __restrict__ h_out, int* __restrict__ status_out,
@@ -402,13 +416,15 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     bool active = true;
     if constexpr (!FULL) active = agent < c.B;
     const unsigned row_i = active ? slot : sub;            // inactive lanes compute on agent 0, store nothing
-    const unsigned ag_i = row_i >> 3;
+    const unsigned ag8 = row_i & ~7u;                      // agent * 8
 
+    // byte offsets as 32-bit lane values on the scalar bases; launch_coop admits only batches whose slot fits 24 bits
     struct { TIO v[7]; } orow;
-    __builtin_memcpy(&orow, obs + row_i * 7u, sizeof(orow));
-    const V2 ur = reinterpret_cast<const V2*>(u_ref)[ag_i];
-    const StateRow<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D> xs = load_state<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(X, ag_i);
-    fetch_arg_now(c.t0); fetch_arg_now(c.t1); fetch_arg_now(c.k0); fetch_arg_now(c.k1); fetch_arg_now(c.hard);
+    __builtin_memcpy(&orow, at_byte(obs, __umul24(row_i, 7u * (unsigned)sizeof(TIO))), sizeof(orow));
+    const V2 ur = *reinterpret_cast<const V2*>(at_byte(u_ref, ag8 * (unsigned)(sizeof(V2) / 8)));
+    StateRow<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D> xs;
+    __builtin_memcpy(&xs, at_byte(X, ag8 * (unsigned)(sizeof(xs) / 8)), sizeof(xs));
+    fetch_arg_now(c.t0); fetch_arg_now(c.t1); fetch_arg_now(c.k0); fetch_arg_now(c.k1);
 
     SinCosTab sc;
     sc.two_over_pi = c.t0[0]; sc.pio2_1 = c.t0[1]; sc.pio2_2 = c.t0[2]; sc.pio2_3 = c.t0[3];
@@ -417,9 +433,11 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     for (int i = 0; i < 6; ++i) sc.c[i] = c.t1[2 + i];
     CbfConsts<TC> k;                                       // the fields cbf_row<DynamicUnicycle2D> and the solve read; the rest is never looked at
     k.R = c.k0[0]; k.a1 = TC(0); k.a2 = TC(0); k.g1 = c.k0[1]; k.g2 = c.k0[2]; k.inv_dt = c.k0[3]; k.inv_dt2 = c.k0[4];
-    k.lo0 = c.k0[5]; k.hi0 = c.k0[6]; k.lo1 = c.k0[7]; k.hi1 = c.k1[0]; k.inv_Lr = TC(0); k.inv_mass = TC(1); k.hard = c.hard;
+    k.lo0 = c.k0[5]; k.hi0 = c.k0[6]; k.lo1 = c.k0[7]; k.hi1 = c.k1[0]; k.inv_Lr = TC(0); k.inv_mass = TC(1); k.hard = HARD;
     BoxTol<TC> bt;
     bt.lo0 = c.k1[1]; bt.hi0 = c.k1[2]; bt.lo1 = c.k1[3]; bt.hi1 = c.k1[4];
+    SolveLit<TC> lit;
+    lit.tol_feas = c.k1[5]; lit.eps_par = c.k1[6]; lit.inf = c.k1[7];
 
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
     Agent<TC> ag;                                          // make_agent with the constants of its sincos from the argument block
@@ -436,7 +454,7 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     const bool ok = cbf_row<TC, SC_MODEL_DYNAMIC_UNICYCLE2D, false>(ag, o, k, a0, a1, cc, h);
     const bool bad_mine = !ok;
     if constexpr (HAS_H) {
-        if (active) h_out[slot] = TIO(h);
+        if (active) *at_byte(h_out, slot * (unsigned)sizeof(TIO)) = TIO(h);
     }
     TC poison = TC(0);
     normalise_row_as_generic(a0, a1, cc, poison);
@@ -446,13 +464,13 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     // bounds arrive quieted (launch_coop8_du), everything else here is converted from storage or the result of arithmetic.
     QpState<TC> S;
     qp_begin_raw(S, ur0, ur1, k);
-    coop_solve_all8_full<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, bt);
+    coop_solve_all8_full<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, bt, lit);
     qp_finish_box_raw(S, k);
-    TC worst = qp_row_margin_raw(a0, a1, cc, S.u0, S.u1, poison);
+    TC worst = qp_row_margin_raw(a0, a1, cc, S.u0, S.u1, poison, lit);
     const bool nan_mine = !(poison == poison);
     worst = nan_mine ? -num<TC>::inf() : worst;
     worst = min8_raw(worst);
-    int st = qp_status(S, worst, TC(0), k);
+    int st = qp_status_lit(S, worst, TC(0), k, lit);
     if (__builtin_amdgcn_ballot_w64(bad_mine) != 0ull) {   // wave-uniform, cold: the group's byte of the ballot, as in cbfqp_coop_kernel
         asm volatile("");                                  // keeps the block a branch: flattened, its shift and byte test run in every wave
         const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
@@ -509,15 +527,17 @@ static hipError_t launch_coop8_du(const sc_cbfqp_params& p, long long B, const v
     c.t0 = sc_d8{t.two_over_pi, t.pio2_1, t.pio2_2, t.pio2_3, t.s[0], t.s[1], t.s[2], t.s[3]};
     c.t1 = sc_d8{t.s[4], t.s[5], t.c[0], t.c[1], t.c[2], t.c[3], t.c[4], t.c[5]};
     c.k0 = sc_d8{k.R, k.g1, k.g2, k.inv_dt, k.inv_dt2, sc_quieted(k.lo0), sc_quieted(k.hi0), sc_quieted(k.lo1)};
-    c.k1 = sc_d8{sc_quieted(k.hi1), bt.lo0, bt.hi0, bt.lo1, bt.hi1, 0.0, 0.0, 0.0};
-    c.hard = k.hard;
+    // tol_feas, eps_par and +inf of the solve: the bit patterns of num<double> (sc_math.hpp), which is device-only
+    c.k1 = sc_d8{sc_quieted(k.hi1), bt.lo0, bt.hi0, bt.lo1, bt.hi1, 1e-9, 1e-12, __builtin_huge_val()};
     c.B = (unsigned)B;
     const dim3 grid(coop_grid((unsigned)((B + 7) / 8))), block(64);
-#define SC_GO(FULL, HAS_H)                                                                                             \
-    hipLaunchKernelGGL((cbfqp_coop8_du_kernel<TIO, FULL, HAS_H>), grid, block, 0, stream, (const TIO*)obs, (const TIO*)X, \
+#define SC_GO(FULL, HAS_H, HARD)                                                                                             \
+    hipLaunchKernelGGL((cbfqp_coop8_du_kernel<TIO, FULL, HAS_H, HARD>), grid, block, 0, stream, (const TIO*)obs, (const TIO*)X, \
                        (const TIO*)u_ref, (TIO*)u_out, (TIO*)h_out, status, c)
-    if (B % 8 == 0) { if (h_out) SC_GO(true, true); else SC_GO(true, false); }
-    else { if (h_out) SC_GO(false, true); else SC_GO(false, false); }
+#define SC_GO_H(FULL, HAS_H) do { if (k.hard) SC_GO(FULL, HAS_H, true); else SC_GO(FULL, HAS_H, false); } while (0)
+    if (B % 8 == 0) { if (h_out) SC_GO_H(true, true); else SC_GO_H(true, false); }
+    else { if (h_out) SC_GO_H(false, true); else SC_GO_H(false, false); }
+#undef SC_GO_H
 #undef SC_GO
     return hipGetLastError();
 }
@@ -527,10 +547,11 @@ static hipError_t launch_coop(const sc_cbfqp_params& p, long long B, int K, cons
                               const void* obs, const int* n_obs, void* u_out, int* status, void* h_out,
                               hipStream_t stream) {
     // The specialised kernel serves the launches it was written for and nothing else: 8 rows of per-agent obstacles, no n_obs, a
-    // batch in the cooperative regime, and every byte offset below 2^31 (the obstacle block is the largest array of a launch).
+    // batch in the cooperative regime, every byte offset below 2^31 (the obstacle block is the largest array of a launch), and
+    // every row index B * 8 within 24 bits (the kernel forms the row's byte offset with the 24-bit multiply).
     if constexpr (G == 8 && MODEL == SC_MODEL_DYNAMIC_UNICYCLE2D && sizeof(TC) == 8 && SC_COOP_WAVES == 1) {
         if (K == 8 && n_obs == nullptr && p.obs_shared == 0 && B >= 1 && B <= sc_coop_max_agents() &&
-            B * 8 * 7 * (long long)sizeof(TIO) <= 0x7fffffffLL && !sc_cbfqp_generic())
+            B * 8 * 7 * (long long)sizeof(TIO) <= 0x7fffffffLL && B * 8 <= 0xffffffLL && !sc_cbfqp_generic())
             return launch_coop8_du<TIO>(p, B, X, u_ref, obs, u_out, status, h_out, stream);
     }
     constexpr int APW = 64 / G;

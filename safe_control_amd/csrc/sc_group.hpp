@@ -311,13 +311,27 @@ __device__ __forceinline__ void qp_finish_box_raw(QpState<double>& S, const CbfC
     S.u0 = min_raw_s(max_raw_s(S.u0, k.lo0), k.hi0);
     S.u1 = min_raw_s(max_raw_s(S.u1, k.lo1), k.hi1);
 }
+// The literals of the specialised solve as wave-uniform values from the argument block (Coop8Consts::k1, filled by launch_coop8_du
+// with the bit patterns of num<double>): as a literal each is two s_mov_b32 in front of every instruction that names it, rebuilt
+// per use; as an SGPR pair that the wave has fetched anyway it is the instruction's scalar operand.  Same operations, same values.
+template <typename T>
+struct SolveLit { T tol_feas, eps_par, inf; };
+
 // qp_row_margin (sc_qp2.hpp) of one row against worst = +inf, with max(1, |ci|) as one instruction: ci is the product of
 // arithmetic (normalise_row), never a signalling NaN.
-__device__ __forceinline__ double qp_row_margin_raw(double a0, double a1, double ci, double u0, double u1, double& poison) {
+__device__ __forceinline__ double qp_row_margin_raw(double a0, double a1, double ci, double u0, double u1, double& poison,
+                                                    const SolveLit<double>& lit) {
     const double s = a0 * u0 + (a1 * u1 + ci);
-    const double m = s + num<double>::tol_feas() * max_abs_one_raw(ci);
+    const double m = s + lit.tol_feas * max_abs_one_raw(ci);
     poison += 0.0 * s;
-    return fmin_(num<double>::inf(), m);
+    return fmin_(lit.inf, m);
+}
+// qp_status (sc_qp2.hpp) with the infinity of its finiteness test from the argument block: !(|x| < inf) is "inf or NaN"
+__device__ __forceinline__ int qp_status_lit(const QpState<double>& S, double worst, double poison, const CbfConsts<double>& k,
+                                             const SolveLit<double>& lit) {
+    const bool finite = (poison == poison) && (fabs_(S.ur0 + S.ur1) < lit.inf);
+    const bool box_ok = (k.lo0 <= k.hi0) && (k.lo1 <= k.hi1);
+    return (!(worst >= 0.0) || !finite || !box_ok) ? SC_STATUS_INFEASIBLE : SC_STATUS_OPTIMAL;
 }
 
 // clip_box_tol with the flat directions (d == 0: the selects, the four `inside` compares, the +-inf literals) under one branch.
@@ -336,23 +350,40 @@ __device__ __forceinline__ void clip_box_tol_lazy(LineQP<T>& L, const CbfConsts<
 }
 
 // clip_row_coop with the parallel-row test made lazy: `dead` needs par_viol only where the partner is parallel to the line
-// (!pos && !neg), so the loop keeps "some partner was parallel" and the caller takes one wave-uniform branch on its ballot
-// (partners8_dead below).  The restriction of the interval is clip_row_coop's, operation for operation.
-template <typename T>
-__device__ __forceinline__ void clip_row_coop_lazy(LineQP<T>& L, bool& anypar, T g0, T g1, T gc) {
-    const T a = g0 * L.d0 + g1 * L.d1;
-    const T r = g0 * L.p0 + (g1 * L.p1 + gc);
-    const bool pos = a > num<T>::eps_par();
-    const bool neg = !(a >= -num<T>::eps_par());
-    const T q = r * rcp_(fabs_(a));
-    anypar |= !pos && !neg;
+// (!pos && !neg, i.e. |a| <= eps_par), so the clip hands back its `a`, the loop keeps the smallest |a| of the seven partners -- one
+// vector instruction per partner, the |.| a source modifier, where a flag took an s_xor and an s_or each -- and the caller takes
+// one wave-uniform branch on ballot(min |a| <= eps_par) (partners8_dead below).  min |a| <= eps exactly when some |a| <= eps; a NaN
+// `a` is not parallel in clip_row_coop (`neg` holds) and the raw minimum passes it over, and seven NaNs leave a NaN, which fails
+// the compare.  The restriction of the interval is clip_row_coop's, operation for operation; eps_par is an SGPR operand.
+__device__ __forceinline__ double min_abs_abs_raw(double a, double b) { double r; asm("v_min_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
+__device__ __forceinline__ double min_abs_raw(double a, double b) { double r; asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }     // min(a, |b|)
+__device__ __forceinline__ double clip_row_coop_lazy(LineQP<double>& L, double eps, double g0, double g1, double gc) {
+    const double a = g0 * L.d0 + g1 * L.d1;
+    const double r = g0 * L.p0 + (g1 * L.p1 + gc);
+    const bool pos = a > eps;
+    const bool neg = !(a >= -eps);
+    const double q = r * rcp_(fabs_(a));
     L.lo = max_neg_raw(L.lo, keep_or_nan(pos, q));
     L.hi = min_raw(L.hi, keep_or_nan(neg, q));
+    return a;
 }
-template <typename TC, int... Xs>
-__device__ __forceinline__ void clip_partners8_lazy(LineQP<TC>& L, bool& anypar, TC a0, TC a1, TC cc, std::integer_sequence<int, Xs...>) {
-    const TC m0 = dpp_mov<0x141>(a0), m1 = dpp_mov<0x141>(a1), mc = dpp_mov<0x141>(cc);
-    (clip_row_coop_lazy(L, anypar, group_xor8<TC, Xs + 1>(a0, m0), group_xor8<TC, Xs + 1>(a1, m1), group_xor8<TC, Xs + 1>(cc, mc)), ...);
+template <int X>
+__device__ __forceinline__ double clip_partner8_lazy(LineQP<double>& L, double eps, double a0, double a1, double cc, double m0, double m1,
+                                                     double mc) {
+    return clip_row_coop_lazy(L, eps, group_xor8<double, X>(a0, m0), group_xor8<double, X>(a1, m1), group_xor8<double, X>(cc, mc));
+}
+// the seven partners in the order of clip_partners8; returns the smallest |a|
+__device__ __forceinline__ double clip_partners8_lazy(LineQP<double>& L, double eps, double a0, double a1, double cc) {
+    const double m0 = dpp_mov<0x141>(a0), m1 = dpp_mov<0x141>(a1), mc = dpp_mov<0x141>(cc);
+    const double x1 = clip_partner8_lazy<1>(L, eps, a0, a1, cc, m0, m1, mc);
+    const double x2 = clip_partner8_lazy<2>(L, eps, a0, a1, cc, m0, m1, mc);
+    double amin = min_abs_abs_raw(x1, x2);
+    amin = min_abs_raw(amin, clip_partner8_lazy<3>(L, eps, a0, a1, cc, m0, m1, mc));
+    amin = min_abs_raw(amin, clip_partner8_lazy<4>(L, eps, a0, a1, cc, m0, m1, mc));
+    amin = min_abs_raw(amin, clip_partner8_lazy<5>(L, eps, a0, a1, cc, m0, m1, mc));
+    amin = min_abs_raw(amin, clip_partner8_lazy<6>(L, eps, a0, a1, cc, m0, m1, mc));
+    amin = min_abs_raw(amin, clip_partner8_lazy<7>(L, eps, a0, a1, cc, m0, m1, mc));
+    return amin;
 }
 // the cold block: `dead` of clip_row_coop for one partner / for the seven, from the line as clip_box left it (p and d do not
 // change in the clips) -- the same a, r and par_viol, so the same flag.  The partners come by shuffles in a loop that stays
@@ -378,20 +409,21 @@ __device__ __forceinline__ bool partners8_dead(const LineQP<TC>& L, TC a0, TC a1
 // the raw min / max of the clips (inline assembly, so the compiler cannot see that they are canonical); those return one of their
 // operands or a quieted NaN, and their operands are products of arithmetic.  Operand order as the compiler emits it for the
 // expressions of coop_pick_winner: max(lo, 0), then min(., hi); max(|lo|, |hi|), then max(., 1).
-__device__ __forceinline__ void coop_pick_winner8_raw(QpState<double>& S, const LineQP<double>& L, bool ok, int sub, int lane) {
+__device__ __forceinline__ void coop_pick_winner8_raw(QpState<double>& S, const LineQP<double>& L, bool ok, int sub, int lane,
+                                                      const SolveLit<double>& lit) {
     using TC = double;
-    const TC inf = num<TC>::inf();
+    const TC inf = num<TC>::inf();                                              // of the select, whose high word needs a VGPR anyway
     TC t = min_raw(max_zero_raw(L.lo), L.hi);
     const bool inverted = L.lo > L.hi;
     t = inverted ? TC(0.5) * (L.lo + L.hi) : t;
-    const bool empty = L.lo > L.hi + num<TC>::tol_feas() * max_one_raw(max_abs_abs_raw(L.lo, L.hi));
+    const bool empty = L.lo > L.hi + lit.tol_feas * max_one_raw(max_abs_abs_raw(L.lo, L.hi));
     const TC v0 = L.p0 + t * L.d0, v1 = L.p1 + t * L.d1;
     const TC e0 = v0 - S.ur0, e1 = v1 - S.ur1;
     TC cost = e0 * e0 + e1 * e1;
     cost = (ok && !empty && (cost == cost)) ? cost : inf;
     const TC best = min8_raw(cost);
     bool has;
-    const bool mine = group_first<8>(__builtin_amdgcn_ballot_w64((cost == best) && (best < inf)), lane, sub, has);
+    const bool mine = group_first<8>(__builtin_amdgcn_ballot_w64((cost == best) && (best < lit.inf)), lane, sub, has);
     const TC s0 = group_pick<8>(mine, v0), s1 = group_pick<8>(mine, v1);
     S.u0 = has ? s0 : S.u0;
     S.u1 = has ? s1 : S.u1;
@@ -400,18 +432,17 @@ __device__ __forceinline__ void coop_pick_winner8_raw(QpState<double>& S, const 
 // coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`), the box bounds above and the cold paths out of the way
 template <typename TC>
 __device__ __forceinline__ void coop_solve_all8_full(QpState<TC>& S, int sub, int lane, TC a0, TC a1, TC cc,
-                                                     const CbfConsts<TC>& k, const BoxTol<TC>& bt) {
+                                                     const CbfConsts<TC>& k, const BoxTol<TC>& bt, const SolveLit<TC>& lit) {
     const bool testable = !((a0 == TC(0)) && (a1 == TC(0)));
     LineQP<TC> L;
     const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;
     if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;
     clip_box_tol_lazy(L, k, bt);
-    bool anypar = false;
-    clip_partners8_lazy(L, anypar, a0, a1, cc, std::make_integer_sequence<int, 7>{});
+    const TC amin = clip_partners8_lazy(L, lit.eps_par, a0, a1, cc);
     bool dead = false;
-    if (__builtin_amdgcn_ballot_w64(anypar) != 0ull)                         // wave-uniform, cold: some row of the wave parallel to some line
+    if (__builtin_amdgcn_ballot_w64(amin <= lit.eps_par) != 0ull)             // wave-uniform, cold: some row of the wave parallel to some line
         dead = partners8_dead(L, a0, a1, cc);
-    coop_pick_winner8_raw(S, L, viol && !dead, sub, lane);
+    coop_pick_winner8_raw(S, L, viol && !dead, sub, lane, lit);
 }
 
 // The same for 16 lanes per agent (K <= 16; one DPP row per agent): fifteen partners by row_ror, reductions by quad permutes and

@@ -6,7 +6,12 @@ normalises them, and are grouped as the kernel groups them: 8 agents of 8 rows p
 violated at u_box = clamp(u_ref)) takes
   * the flat-direction block of clip_box_tol_lazy when a unit normal of ANY of its rows has a component that is exactly 0.0,
   * the parallel-partner block of coop_solve_all8_full when two rows of one agent have |n_i x n_j| <= eps_par (1e-12),
-  * the bad-obstacle block of the tail when a row's flag is neither 0 nor 1 (that one in every wave, entering the solve or not).
+  * the bad-obstacle block of the tail when a row's flag is neither 0 nor 1 (that one in every wave, entering the solve or not),
+  * the select of normalise_row_as_generic when some row has not nn > 0 -- an all-zero row, a normal whose squares underflow, a
+    NaN, a bad row (the kernel zeroes it) -- in every wave, entering the solve or not.
+The parallel-partner flag of the kernel is ballot(min over the seven partners of |a| <= eps_par), a = n_partner . d_line, which is
+|n_i x n_j| of the unit normals: the same set of waves as the per-partner flags it replaced.  A wave-uniform test on "any flag
+other than 0 in the wave" (the dispatch of cbf_row) is counted as well; the kernel does not branch on it.
 The oracle's rows differ from the kernel's in the last bits (its sincos is the C library's), so a pair that sits within a few ulp
 of eps_par could be counted differently; the smallest |n_i x n_j| and the smallest |component| of the batch are printed so that the
 distance to the thresholds can be seen.
@@ -28,8 +33,13 @@ EPS_PAR = 1e-12
 
 def unit_rows(X, obs, spec, cbf_mode="cbf"):
     """Normalised rows (n[B, K, 2], c[B, K]) and the bad-row mask of a batch, by the numpy oracle."""
+    return unit_rows_nn(X, obs, spec, cbf_mode)[:3]
+
+
+def unit_rows_nn(X, obs, spec, cbf_mode="cbf"):
+    """unit_rows and nn[B, K], the sum of squares each row was normalised by (0 for a bad row: the kernel zeroes it)."""
     B, K = obs.shape[:2]
-    n = np.zeros((B, K, 2)); c = np.zeros((B, K)); bad = np.zeros((B, K), dtype=bool)
+    n = np.zeros((B, K, 2)); c = np.zeros((B, K)); bad = np.zeros((B, K), dtype=bool); nns = np.zeros((B, K))
     cp = ocbf.default_cbf_param(R.MODEL_DU)
     for i in range(B):
         for r in range(K):
@@ -42,12 +52,14 @@ def unit_rows(X, obs, spec, cbf_mode="cbf"):
             s = 1.0 / np.sqrt(nn) if nn > 0 else 1.0
             n[i, r] = A[0] * s
             c[i, r] = b[0] * s
-    return n, c, bad
+            nns[i, r] = nn
+    return n, c, bad, nns
 
 
 def conditions(X, u_ref, obs, spec, cbf_mode="cbf"):
-    """Per agent: violated rows at u_box, rows with an exactly zero component, parallel pairs, bad rows; and the two minima."""
-    n, c, bad = unit_rows(X, obs, spec, cbf_mode)
+    """Per agent: violated rows at u_box, rows with an exactly zero component, parallel pairs, bad rows, rows whose flag is not a
+    circle's, rows without nn > 0, the matrix of |n_i x n_j|; and the two minima."""
+    n, c, bad, nns = unit_rows_nn(X, obs, spec, cbf_mode)
     lo, hi = ocbf.input_bounds(R.MODEL_DU, spec)
     ubox = np.clip(u_ref, lo, hi)
     zero_row = (n[:, :, 0] == 0) & (n[:, :, 1] == 0)
@@ -57,7 +69,9 @@ def conditions(X, u_ref, obs, spec, cbf_mode="cbf"):
     K = n.shape[1]
     off = ~np.eye(K, dtype=bool)[None] & ~bad[:, :, None] & ~bad[:, None, :]
     par = (cross <= EPS_PAR) & off
-    return dict(viol=viol, flat=flat, par=par, bad=bad, min_cross=float(cross[np.broadcast_to(off, cross.shape)].min()),
+    with np.errstate(invalid="ignore"):
+        degenerate = ~(nns > 0)
+    return dict(viol=viol, flat=flat, par=par, bad=bad, noncircle=obs[:, :, 6] != 0, degenerate=degenerate, cross=cross, min_cross=float(cross[np.broadcast_to(off, cross.shape)].min()),
                 min_comp=float(np.abs(n[~bad]).min()))
 
 
@@ -77,12 +91,16 @@ def main():
     flat = wave(c["flat"].any(axis=1)) & enters
     par = wave(c["par"].any(axis=(1, 2))) & enters
     bad = wave(c["bad"].any(axis=1))
+    noncircle = wave(c["noncircle"].any(axis=1))
+    degenerate = wave(c["degenerate"].any(axis=1))
     nv = c["viol"].sum(axis=1)
     print(f"{len(enters)} waves, {int(enters.sum())} enter the solve; violated rows per agent: max {int(nv.max())}, "
           f"{int((nv >= 2).sum())} agents with two or more")
     print(f"waves that take the flat-direction block: {int(flat.sum())}   (smallest |component| of a unit normal: {c['min_comp']:.3e})")
     print(f"waves that take the parallel-partner block: {int(par.sum())}   (smallest |n_i x n_j|: {c['min_cross']:.3e}, threshold {EPS_PAR:g})")
     print(f"waves that take the bad-obstacle block: {int(bad.sum())}")
+    print(f"waves with a row that has not nn > 0 (the select of the normalisation): {int(degenerate.sum())}")
+    print(f"waves that hold a flag other than 0 (not branched on): {int(noncircle.sum())}")
 
 
 if __name__ == "__main__":
