@@ -291,6 +291,9 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TI
     }
     return;
 #endif
+    // From here to the stores this body has a second copy: coop8_generic_body below restates it, function by function, for the
+    // waves that leave the specialised kernel's fast path, and must return the same bits (tests/test_cbfqp_exits_gpu.py).  A
+    // change to the sequence here is mirrored there.
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
     const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
 
@@ -358,11 +361,23 @@ __global__ __launch_bounds__(64 * SC_COOP_WAVES) void cbfqp_coop_kernel(const TI
 //   * FULL: B is a multiple of the 8 agents of a wave, so there is no `active` guard at all; !FULL keeps it (c.B);
 //   * HAS_H: h_out is non-null;
 //   * the obstacle row arrives with two loads (16 + 12 bytes, f32 storage) instead of seven;
-//   * the f64 sincos reads its sixteen constants, and clip_box its `lo - tol` / `hi + tol`, from the argument block;
-//   * what only a rare wave needs -- a flat direction of the box clip, a partner row parallel to a line, a bad obstacle flag -- sits
-//     under one wave-uniform branch each, and the min / max of values that cannot be signalling NaNs skip the canonicalising
-//     v_max(x, x) (sc_group.hpp, "cold paths of the specialised solve"; tests/test_cbfqp_coldpaths_gpu.py runs the cold blocks).
-// Arithmetic and its order are those of the generic kernel, so both return the same bits (tests/test_cbfqp_special_gpu.py).
+//   * the f64 sincos reads its sixteen constants, and the solve its literals (SolveLit), from the argument block;
+//   * every lane is taken as ordinary: a circle (flag 0), |theta| < 1e5 (the table sincos), a row with nn > 0, no flat direction of
+//     the box clip, no partner row parallel to its line -- and the min / max of values that cannot be signalling NaNs skip the
+//     canonicalising v_max(x, x) (sc_group.hpp, "the solve of the specialised K = 8 kernel").
+// A wave that holds a lane which is not ordinary leaves the fast path through one of two wave-uniform exits, and both lead to the
+// same place: the generic K = 8 sequence for the whole wave (coop8_generic_body: the functions cbfqp_coop_kernel calls, in its order,
+// on the inputs this kernel has loaded), which stores h itself and hands u and status to the kernel's store.
+//   * early exit, as soon as the inputs have landed: some lane's flag is not 0, or not |theta| < 1e5 (a NaN included: the arm
+//     sincos_ takes for it).  Both are visible in the inputs, so such a wave -- a fleet among superellipsoids -- pays for no fast path;
+//   * late exit, one scalar test in front of the u / status stores: some lane met a row without nn > 0, a flat direction or a
+//     parallel partner.  The flag is an OR of wave masks that only grows, so a predicate computed from state an earlier oddity has spoiled cannot clear
+//     it; the row test sits in front of the solve's own early-out, which therefore cannot bypass it.  The fast path may have stored
+//     an h by then: the generic sequence stores it again, and the later store to the same address wins.  A flag that is neither 0
+//     nor 1 (the bad obstacle) is a flag that is not 0: it leaves through the early exit.
+// On an ordinary wave both branches fall through and no cold code lies between the entry and s_endpgm (tools/coop8_path_count.py).
+// Arithmetic and its order on the fast path are those of the generic kernel, so both return the same bits
+// (tests/test_cbfqp_special_gpu.py, tests/test_cbfqp_exits_gpu.py).
 // Six pointers in order of first use are preloaded (12 dwords); n_obs, B, K and obs_shared are not arguments.
 // The constants travel as four 64-byte vectors so that a wave fetches them with four scalar loads (field by field the compiler
 // emits one load per double: two dozen executed instructions).  Filled by launch_coop8_du, taken apart at the top of the kernel.
@@ -371,25 +386,47 @@ struct Coop8Consts {
     sc_d8 t0;                                              // SinCosTab: two_over_pi, pio2_1, pio2_2, pio2_3, s[0..3]
     sc_d8 t1;                                              //            s[4], s[5], c[0..5]
     sc_d8 k0;                                              // R, g1, g2, inv_dt, inv_dt2, lo0, hi0, lo1
-    sc_d8 k1;                                              // hi1, BoxTol: lo0, hi0, lo1, hi1; SolveLit: tol_feas, eps_par, +inf
+    sc_d8 k1;                                              // hi1; SolveLit: th_max, neg_beta; two spares; tol_feas, eps_par, +inf
     unsigned B;                                            // read by the !FULL instantiations only
 };
 
-// normalise_row with the sum of squares written as the fused form the generic kernel compiles to.  `n0 * n0 + n1 * n1` leaves it to
-// the compiler which product stays a rounded multiply and which goes into the FMA; behind the generic kernel's `used` selects it
-// picks fma(n1, n1, n0 * n0), without them (here) the other one, and the two differ in the last bit of some rows.
-// The guard `nn > 0 ? rsqrt_(nn) : 1` is off the path of an ordinary wave: the reciprocal square root is taken of every lane with the
-// whole wave enabled (v_rsq_f64 of 0, a negative or a NaN traps nothing), and only a wave in which some row has not nn > 0
-// (all-zero, underflowed, NaN) runs the select, which puts 1.0 where it is today.  Every lane gets the bits it got.
-__device__ __forceinline__ void normalise_row_as_generic(double& n0, double& n1, double& c, double& poison) {
+// The circle row of cbf_row<double, DynamicUnicycle2D> (hocbf_circle and the tail of cbf_row) with every sum of products written
+// as the fused form the generic kernel compiles to.  `x * y + z * w` leaves it to the compiler which product stays a rounded
+// multiply and which goes into the FMA, and the choice depends on the surrounding code: outside cbf_row's flag branches it picks
+// the other product for Lf, and the two differ in the last bit of some rows.  The forms below are read, sum by sum, from the
+// gfx950 listing of cbfqp_coop_kernel<float, double, 8, 0> (x * y + z * w in source order; "rounded" is the plain multiply):
+//   ex ex + ey ey       fma(ex, ex, ey * ey)          first product fused, second rounded
+//   (..) - beta dmin^2  fma(dmin, dmin * -1.01, ..)   dmin * -1.01 rounded ( = -(1.01 dmin) exactly), then fused with dmin
+//   hdot                2 fma(ex, f0, ey * f1)        first fused, second rounded
+//   n1 = dhd[2]         2 fma(ey, f0, -(ex * f1))     the SECOND product fused; the first, ex * (-f1), rounded, its sign folded
+//   n0 = dhd[3]         2 fma(ex, c, ey * s)          first fused, second rounded
+//   Lf                  fma(dhd0, f0, dhd1 * f1)      first fused, second rounded
+//   c, soft             fma(g2, h, fma(g1, hdot, Lf)) ; c, hard: fma(h, inv_dt2, (2 hdot) inv_dt) + Lf, the last a plain add
+// 2 x is x + x exactly, so where the factor 2 is applied does not matter.
+template <bool HARD>
+__device__ __forceinline__ void circle_row_du_as_generic(const Agent<double>& a, const double* o, const CbfConsts<double>& k,
+                                                         double neg_beta, double& n0, double& n1, double& c, double& h) {
+    const double ex = a.x - o[0], ey = a.y - o[1];
+    const double dmin = o[2] + k.R;
+    h = __builtin_fma(dmin, dmin * neg_beta, __builtin_fma(ex, ex, ey * ey));
+    const double hdot = 2.0 * __builtin_fma(ex, a.f0, ey * a.f1);
+    const double dhd0 = 2.0 * a.f0, dhd1 = 2.0 * a.f1;
+    n1 = 2.0 * __builtin_fma(ey, a.f0, -(ex * a.f1));      // dhd[2] = 2 (ex (-f1) + ey f0)
+    n0 = 2.0 * __builtin_fma(ex, a.c, ey * a.s);           // dhd[3]
+    const double Lf = __builtin_fma(dhd0, a.f0, dhd1 * a.f1);
+    if constexpr (HARD) c = __builtin_fma(h, k.inv_dt2, (2.0 * hdot) * k.inv_dt) + Lf;
+    else c = __builtin_fma(k.g2, h, __builtin_fma(k.g1, hdot, Lf));
+}
+
+// normalise_row with the sum of squares written as the fused form the generic kernel compiles to (behind its `used` selects the
+// compiler picks fma(n1, n1, n0 * n0), without them the other one) and without the guard `nn > 0 ? rsqrt_(nn) : 1`: a row without
+// nn > 0 (all-zero, underflowed, NaN) is reported, and its wave runs normalise_row itself (coop8_generic_body).
+__device__ __forceinline__ bool normalise_row_fast(double& n0, double& n1, double& c, double& poison) {
     const double nn = __builtin_fma(n1, n1, n0 * n0);
     poison += 0.0 * (nn + c);
-    double inv = rsqrt_(nn);
-    if (__builtin_amdgcn_ballot_w64(!(nn > 0.0)) != 0ull) {                   // wave-uniform, cold
-        asm volatile("");
-        inv = nn > 0.0 ? inv : 1.0;
-    }
+    const double inv = rsqrt_(nn);
     n0 *= inv; n1 *= inv; c *= inv;
+    return !(nn > 0.0);
 }
 
 // base + off bytes, off a 32-bit lane value: the scalar-base form of the global loads and stores (no 64-bit address arithmetic)
@@ -397,6 +434,51 @@ template <typename T>
 __device__ __forceinline__ T* at_byte(T* base, unsigned off) {
     using C = typename std::conditional<std::is_const<T>::value, const char, char>::type;
     return reinterpret_cast<T*>(reinterpret_cast<C*>(base) + off);
+}
+
+// Where both exits of cbfqp_coop8_du_kernel lead: the body of cbfqp_coop_kernel<TIO, double, 8, DynamicUnicycle2D> from the loaded
+// inputs to its stores, restated from the same device functions in the same order.  K and nk are 8 here, but they are handed
+// over as run-time values (an empty asm), as they are in that kernel: its `used` and `sub < K` selects then stay in place, and with
+// them the way the compiler fuses the sums of products behind them (see normalise_row_fast), which is what keeps the bits.
+template <typename TIO, bool HAS_H>
+__device__ __forceinline__ void coop8_generic_body(const TIO* orow, typename vec2<TIO>::type ur,
+                                                   const StateRow<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>& xs, bool active,
+                                                   unsigned slot, int sub, int lane, const CbfConsts<double>& k,
+                                                   TIO* __restrict__ h_out, typename vec2<TIO>::type& uo, int& st) {
+    using TC = double;
+    constexpr int MODEL = SC_MODEL_DYNAMIC_UNICYCLE2D;
+    int K = 8, nk = 8;
+    asm volatile("" : "+s"(K), "+s"(nk));
+    const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
+    const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
+    TC o[7];
+#pragma unroll
+    for (int f = 0; f < 7; ++f) o[f] = TC(orow[f]);
+    TC h, a0, a1, cc;
+    const bool ok = cbf_row<TC, MODEL, false>(ag, o, k, a0, a1, cc, h);
+    const bool used = sub < nk;
+    const bool bad_mine = used && !ok;
+    a0 = used ? a0 : TC(0); a1 = used ? a1 : TC(0); cc = used ? cc : TC(0);
+    if constexpr (HAS_H) {
+        if (active && sub < K) *at_byte(h_out, slot * (unsigned)sizeof(TIO)) = used ? TIO(h) : TIO(0);
+    }
+    TC poison = TC(0);
+    normalise_row(a0, a1, cc, poison);
+    QpState<TC> S;
+    qp_begin(S, ur0, ur1, k);
+    coop_solve_all8<TC>(S, K, sub, lane, a0, a1, cc, k);
+    qp_finish_box(S, k);
+    TC worst = qp_row_margin(num<TC>::inf(), a0, a1, cc, S.u0, S.u1, poison);
+    const bool nan_mine = !(poison == poison);
+    worst = nan_mine ? -num<TC>::inf() : worst;
+    worst = min8_raw(worst);
+    const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
+    const bool bad_any = ((bad_mask >> (lane & ~7)) & 0xffull) != 0ull;
+    st = qp_status(S, worst, TC(0), k);
+    if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
+    TC u0 = S.u0, u1 = S.u1;
+    if (st != SC_STATUS_OPTIMAL) { u0 = num<TC>::nan(); u1 = num<TC>::nan(); }
+    uo.x = TIO(u0); uo.y = TIO(u1);
 }
 
 template <typename TIO, bool FULL, bool HAS_H, bool HARD>
@@ -426,65 +508,73 @@ __global__ __launch_bounds__(64) void cbfqp_coop8_du_kernel(const TIO* __restric
     __builtin_memcpy(&xs, at_byte(X, ag8 * (unsigned)(sizeof(xs) / 8)), sizeof(xs));
     fetch_arg_now(c.t0); fetch_arg_now(c.t1); fetch_arg_now(c.k0); fetch_arg_now(c.k1);
 
+    CbfConsts<TC> k;                                       // the fields cbf_row<DynamicUnicycle2D> and the solve read; the rest is never looked at
+    k.R = c.k0[0]; k.a1 = TC(0); k.a2 = TC(0); k.g1 = c.k0[1]; k.g2 = c.k0[2]; k.inv_dt = c.k0[3]; k.inv_dt2 = c.k0[4];
+    k.lo0 = c.k0[5]; k.hi0 = c.k0[6]; k.lo1 = c.k0[7]; k.hi1 = c.k1[0]; k.inv_Lr = TC(0); k.inv_mass = TC(1); k.hard = HARD;
+    SolveLit<TC> lit;
+    lit.th_max = c.k1[1]; lit.neg_beta = c.k1[2]; lit.tol_feas = c.k1[5]; lit.eps_par = c.k1[6]; lit.inf = c.k1[7];
+
+    // ---- early exit: a flag other than 0, or the library arm of sincos_ (its own test, so a NaN theta goes where it sends it) ----
+    const TC th = TC(xs.v[2]);
+    const bool early = (orow.v[6] != TIO(0)) || !(fabs(th) < lit.th_max);
+    const auto store_u_status = [&](V2 uo, int st) {
+        if (active && sub == 0) {
+            reinterpret_cast<V2*>(u_out)[agent] = uo;
+            status_out[agent] = st;
+        }
+    };
+    if (__builtin_expect(__builtin_amdgcn_ballot_w64(early) != 0ull, 0)) {
+        V2 uo; int st;
+        coop8_generic_body<TIO, HAS_H>(orow.v, ur, xs, active, slot, (int)sub, (int)lane, k, h_out, uo, st);
+        store_u_status(uo, st);
+        return;
+    }
     SinCosTab sc;
     sc.two_over_pi = c.t0[0]; sc.pio2_1 = c.t0[1]; sc.pio2_2 = c.t0[2]; sc.pio2_3 = c.t0[3];
     sc.s[0] = c.t0[4]; sc.s[1] = c.t0[5]; sc.s[2] = c.t0[6]; sc.s[3] = c.t0[7]; sc.s[4] = c.t1[0]; sc.s[5] = c.t1[1];
 #pragma unroll
     for (int i = 0; i < 6; ++i) sc.c[i] = c.t1[2 + i];
-    CbfConsts<TC> k;                                       // the fields cbf_row<DynamicUnicycle2D> and the solve read; the rest is never looked at
-    k.R = c.k0[0]; k.a1 = TC(0); k.a2 = TC(0); k.g1 = c.k0[1]; k.g2 = c.k0[2]; k.inv_dt = c.k0[3]; k.inv_dt2 = c.k0[4];
-    k.lo0 = c.k0[5]; k.hi0 = c.k0[6]; k.lo1 = c.k0[7]; k.hi1 = c.k1[0]; k.inv_Lr = TC(0); k.inv_mass = TC(1); k.hard = HARD;
-    BoxTol<TC> bt;
-    bt.lo0 = c.k1[1]; bt.hi0 = c.k1[2]; bt.lo1 = c.k1[3]; bt.hi1 = c.k1[4];
-    SolveLit<TC> lit;
-    lit.tol_feas = c.k1[5]; lit.eps_par = c.k1[6]; lit.inf = c.k1[7];
-
     const TC ur0 = TC(ur.x), ur1 = TC(ur.y);
-    Agent<TC> ag;                                          // make_agent with the constants of its sincos from the argument block
-    ag.x = TC(xs.v[0]); ag.y = TC(xs.v[1]); ag.th = TC(xs.v[2]); ag.v = TC(xs.v[3]);
+    Agent<TC> ag;                                      // make_agent with the constants of its sincos from the argument block
+    ag.x = TC(xs.v[0]); ag.y = TC(xs.v[1]); ag.th = th; ag.v = TC(xs.v[3]);
     sincos_tab_sfma(ag.th, sc, &ag.s, &ag.c);
     ag.f0 = ag.v * ag.c;
     ag.f1 = ag.v * ag.s;
 
-    // ---- this lane's row -------------------------------------------------------------------
-    TC o[7];
+    // ---- this lane's row: a circle --------------------------------------------------------
+    TC o[3];
 #pragma unroll
-    for (int f = 0; f < 7; ++f) o[f] = TC(orow.v[f]);
+    for (int f = 0; f < 3; ++f) o[f] = TC(orow.v[f]);
     TC h, a0, a1, cc;
-    const bool ok = cbf_row<TC, SC_MODEL_DYNAMIC_UNICYCLE2D, false>(ag, o, k, a0, a1, cc, h);
-    const bool bad_mine = !ok;
+    circle_row_du_as_generic<HARD>(ag, o, k, lit.neg_beta, a0, a1, cc, h);
     if constexpr (HAS_H) {
         if (active) *at_byte(h_out, slot * (unsigned)sizeof(TIO)) = TIO(h);
     }
     TC poison = TC(0);
-    normalise_row_as_generic(a0, a1, cc, poison);
+    const unsigned long long odd_row = __builtin_amdgcn_ballot_w64(normalise_row_fast(a0, a1, cc, poison));
 
-    // ---- the solve, the slack check and the outputs: as in cbfqp_coop_kernel ------------------
-    // The *_raw forms (sc_group.hpp) are qp_begin / qp_finish_box / qp_row_margin without the canonicalising v_max(x, x): the box
-    // bounds arrive quieted (launch_coop8_du), everything else here is converted from storage or the result of arithmetic.
+    // ---- the solve, the slack check and the outputs: as in cbfqp_coop_kernel ----------------
+    // The *_raw forms (sc_group.hpp) are qp_begin / qp_finish_box / qp_row_margin without the canonicalising v_max(x, x): the
+    // box bounds arrive quieted (launch_coop8_du), everything else here is converted from storage or the result of arithmetic.
     QpState<TC> S;
     qp_begin_raw(S, ur0, ur1, k);
-    coop_solve_all8_full<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, bt, lit);
+    const unsigned long long odd_solve = coop_solve_all8_fast<TC>(S, (int)sub, (int)lane, a0, a1, cc, k, lit);
     qp_finish_box_raw(S, k);
     TC worst = qp_row_margin_raw(a0, a1, cc, S.u0, S.u1, poison, lit);
     const bool nan_mine = !(poison == poison);
     worst = nan_mine ? -num<TC>::inf() : worst;
     worst = min8_raw(worst);
     int st = qp_status_lit(S, worst, TC(0), k, lit);
-    if (__builtin_amdgcn_ballot_w64(bad_mine) != 0ull) {   // wave-uniform, cold: the group's byte of the ballot, as in cbfqp_coop_kernel
-        asm volatile("");                                  // keeps the block a branch: flattened, its shift and byte test run in every wave
-        const unsigned long long bad_mask = __builtin_amdgcn_ballot_w64(bad_mine);
-        const bool bad_any = ((bad_mask >> (lane & ~7u)) & 0xffull) != 0ull;
-        if (bad_any) st = SC_STATUS_BAD_OBSTACLE;
-    }
     TC u0 = S.u0, u1 = S.u1;
     if (st != SC_STATUS_OPTIMAL) { u0 = num<TC>::nan(); u1 = num<TC>::nan(); }
-    if (active && sub == 0) {
-        V2 uo; uo.x = TIO(u0); uo.y = TIO(u1);
-        reinterpret_cast<V2*>(u_out)[agent] = uo;
-        status_out[agent] = st;
-    }
+    V2 uo; uo.x = TIO(u0); uo.y = TIO(u1);
+    // ---- late exit: the lanes' flags as wave masks, so that the test is one scalar OR and one branch; the generic sequence
+    // replaces u and status, which nothing has stored yet, and stores its own h over the fast path's ----------------------
+    if (__builtin_expect((odd_row | odd_solve) != 0ull, 0))
+        coop8_generic_body<TIO, HAS_H>(orow.v, ur, xs, active, slot, (int)sub, (int)lane, k, h_out, uo, st);
+    store_u_status(uo, st);
 }
+
 
 // Developer builds only (tools/README.md): -DSC_EXP_GRID=n launches n workgroups whatever the batch, to time the wave-launch ramp
 // of an empty node.  Only a kernel without a body may run on a grid that is not the batch's.
@@ -521,14 +611,14 @@ template <typename TIO>
 static hipError_t launch_coop8_du(const sc_cbfqp_params& p, long long B, const void* X, const void* u_ref, const void* obs,
                                   void* u_out, int* status, void* h_out, hipStream_t stream) {
     const CbfConsts<double> k = make_consts<double>(p);   // once per launch, on the host
-    const BoxTol<double> bt = box_tol(k);
     const SinCosTab t = make_sincos_tab();
     Coop8Consts c;
     c.t0 = sc_d8{t.two_over_pi, t.pio2_1, t.pio2_2, t.pio2_3, t.s[0], t.s[1], t.s[2], t.s[3]};
     c.t1 = sc_d8{t.s[4], t.s[5], t.c[0], t.c[1], t.c[2], t.c[3], t.c[4], t.c[5]};
     c.k0 = sc_d8{k.R, k.g1, k.g2, k.inv_dt, k.inv_dt2, sc_quieted(k.lo0), sc_quieted(k.hi0), sc_quieted(k.lo1)};
-    // tol_feas, eps_par and +inf of the solve: the bit patterns of num<double> (sc_math.hpp), which is device-only
-    c.k1 = sc_d8{sc_quieted(k.hi1), bt.lo0, bt.hi0, bt.lo1, bt.hi1, 1e-9, 1e-12, __builtin_huge_val()};
+    // the threshold of sincos_ and -beta of hocbf_circle; tol_feas, eps_par and +inf of the solve: the bit patterns of
+    // num<double> (sc_math.hpp), which is device-only
+    c.k1 = sc_d8{sc_quieted(k.hi1), 1.0e5, -1.01, 0.0, 0.0, 1e-9, 1e-12, __builtin_huge_val()};
     c.B = (unsigned)B;
     const dim3 grid(coop_grid((unsigned)((B + 7) / 8))), block(64);
 #define SC_GO(FULL, HAS_H, HARD)                                                                                             \

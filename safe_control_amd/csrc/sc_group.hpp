@@ -249,46 +249,13 @@ __device__ __forceinline__ void coop_solve_all8(QpState<TC>& S, int K, int sub, 
 }
 
 // ---- the solve of the specialised K = 8 kernel (cbfqp_coop8_du_kernel) ---------------------------------------------------
-// clip_box with `lo - tol` and `hi + tol` handed in: the box is wave-uniform and there is no scalar f64 arithmetic on gfx950, so
-// clip_box derives the four sums with vector adds in every wave.  The host computes them with the same two IEEE operations on
-// the same values (box_tol), so `inside` is decided on the same bits.  Everything else is clip_box, line for line.
-template <typename T>
-struct BoxTol { T lo0, hi0, lo1, hi1; };                  // lo0 - tol_feas, hi0 + tol_feas, lo1 - tol_feas, hi1 + tol_feas
-template <typename T>
-__host__ __device__ inline BoxTol<T> box_tol(const CbfConsts<T>& k) {
-    const T tol = sizeof(T) == 8 ? T(1e-9) : T(1e-5f);     // num<T>::tol_feas(), which is device-only
-    BoxTol<T> b;
-    b.lo0 = k.lo0 - tol; b.hi0 = k.hi0 + tol; b.lo1 = k.lo1 - tol; b.hi1 = k.hi1 + tol;
-    return b;
-}
-template <typename T>
-__device__ __forceinline__ void clip_box_tol(LineQP<T>& L, const CbfConsts<T>& k, const BoxTol<T>& bt) {
-    const T inf = num<T>::inf();
-    {
-        const T r = rcp_(L.d0);
-        const T t1 = (k.lo0 - L.p0) * r, t2 = (k.hi0 - L.p0) * r;
-        const bool flat = L.d0 == T(0);
-        const bool inside = (L.p0 >= bt.lo0) && (L.p0 <= bt.hi0);
-        const T lo = flat ? (inside ? -inf : inf) : fmin_(t1, t2);
-        const T hi = flat ? inf : fmax_(t1, t2);
-        L.lo = lo; L.hi = hi;
-    }
-    {
-        const T r = rcp_(L.d1);
-        const T t1 = (k.lo1 - L.p1) * r, t2 = (k.hi1 - L.p1) * r;
-        const bool flat = L.d1 == T(0);
-        const bool inside = (L.p1 >= bt.lo1) && (L.p1 <= bt.hi1);
-        const T lo = flat ? (inside ? -inf : inf) : fmin_(t1, t2);
-        const T hi = flat ? inf : fmax_(t1, t2);
-        L.lo = fmax_(L.lo, lo); L.hi = fmin_(L.hi, hi);
-    }
-}
-// ---- cold paths of the specialised solve -----------------------------------------------------------------------------------
-// What follows serves cbfqp_coop8_du_kernel only.  A lone wave pays for every instruction it executes, and three groups of them
-// decide something that an ordinary wave never needs: a flat direction of the box clip, a partner row parallel to the lane's line,
-// and the canonicalising v_max(x, x) in front of a min / max.  Each rare case moves under ONE wave-uniform branch whose block
-// recomputes the affected values with the operations of the forms above, so every value that can reach an output keeps its bits.
-// How many of the 512 waves of the benchmark batch take each branch is counted in DESIGN.md 1b (none does).
+// What follows serves cbfqp_coop8_du_kernel only.  A lone wave pays for every instruction it executes, so the fast path of that
+// kernel treats every lane as ordinary: no flat direction in the box clip, no partner row parallel to the lane's line, no
+// canonicalising v_max(x, x) in front of a min / max.  It does not repair the rare cases either: each lane reports whether it met
+// one (coop_solve_all8_fast returns the flag), and a wave in which any lane did discards the fast path's result and runs the
+// generic K = 8 sequence (coop_solve_all8 and its neighbours above) from the loaded inputs.  So the forms below only have to be
+// right -- bit for bit what the generic forms give -- for lanes of waves that report nothing.
+// How many of the 512 waves of the benchmark batch report something is counted in DESIGN.md 1b (none does).
 
 // min / max forms whose operands the compiler would canonicalise first (asm outputs, kernel arguments): the argument above
 // min_raw holds for each of them -- see the call sites.  `b` of the *_s forms is wave-uniform (a kernel argument, an SGPR pair).
@@ -315,7 +282,7 @@ __device__ __forceinline__ void qp_finish_box_raw(QpState<double>& S, const CbfC
 // with the bit patterns of num<double>): as a literal each is two s_mov_b32 in front of every instruction that names it, rebuilt
 // per use; as an SGPR pair that the wave has fetched anyway it is the instruction's scalar operand.  Same operations, same values.
 template <typename T>
-struct SolveLit { T tol_feas, eps_par, inf; };
+struct SolveLit { T tol_feas, eps_par, inf, th_max, neg_beta; };   // th_max: 1e5 of sincos_; neg_beta: -1.01 of the circle barrier
 
 // qp_row_margin (sc_qp2.hpp) of one row against worst = +inf, with max(1, |ci|) as one instruction: ci is the product of
 // arithmetic (normalise_row), never a signalling NaN.
@@ -334,27 +301,23 @@ __device__ __forceinline__ int qp_status_lit(const QpState<double>& S, double wo
     return (!(worst >= 0.0) || !finite || !box_ok) ? SC_STATUS_INFEASIBLE : SC_STATUS_OPTIMAL;
 }
 
-// clip_box_tol with the flat directions (d == 0: the selects, the four `inside` compares, the +-inf literals) under one branch.
-// A lane without a flat direction gets fmin_(t1, t2) / fmax_(t1, t2) from both forms; a wave in which some lane has one runs
-// clip_box_tol itself over the whole wave, which overwrites lo / hi with exactly what it gives today.  The ballot is taken over
-// every lane, not only the violated ones: masking it with a flag from another basic block costs two more vector instructions.
+// clip_box for a line without a flat direction: the two reciprocal chains and the min / max, which is what clip_box gives a lane
+// with d0 != 0 and d1 != 0.  A lane with a flat direction gets something else here; the caller reports it.
 template <typename T>
-__device__ __forceinline__ void clip_box_tol_lazy(LineQP<T>& L, const CbfConsts<T>& k, const BoxTol<T>& bt) {
+__device__ __forceinline__ void clip_box_fast(LineQP<T>& L, const CbfConsts<T>& k) {
     const T r0 = rcp_(L.d0), r1 = rcp_(L.d1);
     const T t1 = (k.lo0 - L.p0) * r0, t2 = (k.hi0 - L.p0) * r0;
     const T t3 = (k.lo1 - L.p1) * r1, t4 = (k.hi1 - L.p1) * r1;
-    const bool flat = (L.d0 == T(0)) || (L.d1 == T(0));
     L.lo = fmax_(fmin_(t1, t2), fmin_(t3, t4));
     L.hi = fmin_(fmax_(t1, t2), fmax_(t3, t4));
-    if (__builtin_amdgcn_ballot_w64(flat) != 0ull) clip_box_tol(L, k, bt);             // wave-uniform, cold
 }
 
-// clip_row_coop with the parallel-row test made lazy: `dead` needs par_viol only where the partner is parallel to the line
-// (!pos && !neg, i.e. |a| <= eps_par), so the clip hands back its `a`, the loop keeps the smallest |a| of the seven partners -- one
-// vector instruction per partner, the |.| a source modifier, where a flag took an s_xor and an s_or each -- and the caller takes
-// one wave-uniform branch on ballot(min |a| <= eps_par) (partners8_dead below).  min |a| <= eps exactly when some |a| <= eps; a NaN
-// `a` is not parallel in clip_row_coop (`neg` holds) and the raw minimum passes it over, and seven NaNs leave a NaN, which fails
-// the compare.  The restriction of the interval is clip_row_coop's, operation for operation; eps_par is an SGPR operand.
+// clip_row_coop without its parallel-row test: `dead` needs par_viol only where the partner is parallel to the line (!pos && !neg,
+// i.e. |a| <= eps_par), so the clip hands back its `a`, the loop keeps the smallest |a| of the seven partners -- one vector
+// instruction per partner, the |.| a source modifier -- and the caller reports min |a| <= eps_par.  min |a| <= eps exactly when
+// some |a| <= eps; a NaN `a` is not parallel in clip_row_coop (`neg` holds) and the raw minimum passes it over, and seven NaNs
+// leave a NaN, which fails the compare.  The restriction of the interval is clip_row_coop's, operation for operation; eps_par is
+// an SGPR operand.
 __device__ __forceinline__ double min_abs_abs_raw(double a, double b) { double r; asm("v_min_f64 %0, |%1|, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }
 __device__ __forceinline__ double min_abs_raw(double a, double b) { double r; asm("v_min_f64 %0, %1, |%2|" : "=v"(r) : "v"(a), "v"(b)); return r; }     // min(a, |b|)
 __device__ __forceinline__ double clip_row_coop_lazy(LineQP<double>& L, double eps, double g0, double g1, double gc) {
@@ -385,26 +348,6 @@ __device__ __forceinline__ double clip_partners8_lazy(LineQP<double>& L, double 
     amin = min_abs_raw(amin, clip_partner8_lazy<7>(L, eps, a0, a1, cc, m0, m1, mc));
     return amin;
 }
-// the cold block: `dead` of clip_row_coop for one partner / for the seven, from the line as clip_box left it (p and d do not
-// change in the clips) -- the same a, r and par_viol, so the same flag.  The partners come by shuffles in a loop that stays
-// rolled: the block is cold, and unrolled over DPP moves it is scheduled for overlap and sets the kernel's register count (75).
-template <typename T>
-__device__ __forceinline__ bool row_dead_coop(const LineQP<T>& L, T g0, T g1, T gc) {
-    const T a = g0 * L.d0 + g1 * L.d1;
-    const T r = g0 * L.p0 + (g1 * L.p1 + gc);
-    const bool pos = a > num<T>::eps_par();
-    const bool neg = !(a >= -num<T>::eps_par());
-    const bool par_viol = r < -num<T>::tol_feas() * max_abs_one_raw(gc);
-    return !pos && !neg && par_viol;
-}
-template <typename TC>
-__device__ __forceinline__ bool partners8_dead(const LineQP<TC>& L, TC a0, TC a1, TC cc) {
-    bool dead = false;
-#pragma nounroll
-    for (int x = 1; x < 8; ++x) dead |= row_dead_coop(L, __shfl_xor(a0, x, 8), __shfl_xor(a1, x, 8), __shfl_xor(cc, x, 8));
-    return dead;
-}
-
 // coop_pick_winner for 8 lanes per agent without the v_max(x, x) in front of lo, hi, |lo| and |hi|: the interval ends come out of
 // the raw min / max of the clips (inline assembly, so the compiler cannot see that they are canonical); those return one of their
 // operands or a quieted NaN, and their operands are products of arithmetic.  Operand order as the compiler emits it for the
@@ -429,20 +372,21 @@ __device__ __forceinline__ void coop_pick_winner8_raw(QpState<double>& S, const 
     S.u1 = has ? s1 : S.u1;
 }
 
-// coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`), the box bounds above and the cold paths out of the way
+// coop_solve_all8 with every lane holding a row (K = 8: no `sub < K`) and every lane taken as ordinary.  Returns the lanes that
+// met what this form does not handle -- a flat direction of the box clip or a partner row parallel to the line -- as a wave mask
+// (a scalar: carried across the early-out as a lane flag it would be rebuilt through a VGPR).  A wave that does not enter the
+// solve reports nothing, as it runs neither clip in coop_solve_all8.
 template <typename TC>
-__device__ __forceinline__ void coop_solve_all8_full(QpState<TC>& S, int sub, int lane, TC a0, TC a1, TC cc,
-                                                     const CbfConsts<TC>& k, const BoxTol<TC>& bt, const SolveLit<TC>& lit) {
+__device__ __forceinline__ unsigned long long coop_solve_all8_fast(QpState<TC>& S, int sub, int lane, TC a0, TC a1, TC cc,
+                                                     const CbfConsts<TC>& k, const SolveLit<TC>& lit) {
     const bool testable = !((a0 == TC(0)) && (a1 == TC(0)));
     LineQP<TC> L;
     const bool viol = qp_row_violated(S, a0, a1, cc, L, k) && testable;
-    if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return;
-    clip_box_tol_lazy(L, k, bt);
+    if (__builtin_amdgcn_ballot_w64(viol) == 0ull) return 0ull;
+    clip_box_fast(L, k);
     const TC amin = clip_partners8_lazy(L, lit.eps_par, a0, a1, cc);
-    bool dead = false;
-    if (__builtin_amdgcn_ballot_w64(amin <= lit.eps_par) != 0ull)             // wave-uniform, cold: some row of the wave parallel to some line
-        dead = partners8_dead(L, a0, a1, cc);
-    coop_pick_winner8_raw(S, L, viol && !dead, sub, lane, lit);
+    coop_pick_winner8_raw(S, L, viol, sub, lane, lit);
+    return __builtin_amdgcn_ballot_w64((L.d0 == TC(0)) || (L.d1 == TC(0)) || (amin <= lit.eps_par));
 }
 
 // The same for 16 lanes per agent (K <= 16; one DPP row per agent): fifteen partners by row_ror, reductions by quad permutes and

@@ -98,14 +98,15 @@ __device__ __forceinline__ void sincos_tab(double x, const SinCosTab& t, double*
 // compiler picks the two-address v_fmac_f64 for those steps, whose accumulator must be a VGPR: it copies each constant out of the
 // argument block's SGPRs with a pair of v_mov_b32 first, twenty moves on the short path.  The constant is the addend and the only
 // scalar operand of the instruction, which gfx9 allows.  The first step of each polynomial names two constants and stays with
-// the compiler (one of them goes through a VGPR).  Same operations on the same values in the same order as sincos_tab and sincos_.
+// the compiler (one of them goes through a VGPR).  Same operations on the same values in the same order as the short path of
+// sincos_tab and sincos_, and ONLY that path: there is no library arm here.  The caller (cbfqp_coop8_du_kernel) sends every wave
+// that holds a lane with !(|x| < 1e5) -- a NaN included, which is the arm sincos_ takes for it -- to code that calls sincos_.
 __device__ __forceinline__ double fma_sconst(double a, double b, double c) {        // fma(a, b, c), c wave-uniform
     double d;
     asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(c));
     return d;
 }
 __device__ __forceinline__ void sincos_tab_sfma(double x, const SinCosTab& t, double* s, double* c) {
-    if (!(fabs(x) < 1.0e5)) { sincos(x, s, c); return; }
     const double k = rint(x * t.two_over_pi);
     double r = __builtin_fma(-k, t.pio2_1, x);
     r = __builtin_fma(-k, t.pio2_2, r);

@@ -8,11 +8,13 @@ taken, N = falls through.  A lone wave per SIMD issues one instruction every fou
 walk is what the headline launch pays for.
 
 The default table is the wave the benchmark batch is made of: every lane holds a circle (flag 0), soft mode, |theta| < 1e5, some
-row violated at u_box (the wave enters the solve), and no cold block runs (no flat direction, no parallel partner, no row with
-nn == 0, no bad obstacle).  The table belongs to ONE listing: when the block layout changes, run with --trace, read the condition in
-front of each branch, and write the new table.  --trace prints every conditional branch met with its line, the instruction that
-set its condition and what the table did.  A table that is too short, too long, or names a branch that the walk does not meet
-is an error, not a shorter count.
+row violated at u_box (the wave enters the solve), and neither exit to the generic sequence is taken (no row with nn == 0, no flat
+direction, no parallel partner).  On that path every conditional branch falls through -- the table holds no T -- and the walk
+reaches s_endpgm without jumping over any cold code.  The count of taken branches printed at the end includes the unconditional
+ones the walk follows: it is 1, the s_branch of the kernel-argument preload prologue in front of the entry's code.  The table belongs to ONE
+listing: when the block layout changes, run with --trace, read the condition in front of each branch, and write the new table.
+--trace prints every conditional branch met with its line, the instruction that set its condition and what the table did.  A table
+that is too short, too long, or names a branch that the walk does not meet is an error, not a shorter count.
 
 Instructions are classified by mnemonic prefix only:
   vector   v_* without a DPP control          dpp      v_*_dpp
@@ -34,18 +36,13 @@ CSRC = os.path.join(ROOT, "safe_control_amd", "csrc")
 KERNEL = "cbfqp_coop8_du_kernelIfLb1ELb1ELb0E"     # <float, FULL = true, HAS_H = true, HARD = false>
 
 # One letter per conditional branch on the path of the default wave, in the order the walk meets them (see the docstring).
-#    1  T  the library sincos (|theta| >= 1e5): no lane, skipped
-#    2  N  the table sincos: every lane
-#    3  T  the rows whose flag is not 0: no lane, skipped
-#    4  N  the circle row: every lane
-#    5  T  the select of the normalisation (some row without nn > 0): cold, skipped
-#    6  N  the solve: some row of the wave is violated at u_box
-#    7  T  flat direction of the box clip: cold, skipped
-#    8  T  parallel partner: cold, skipped
-#    9  T  bad obstacle: cold, skipped
-#   10  N  the store of u and status: lane 0 of every group
-# The listing of the commit before (kernel cbfqp_coop8_du_kernelIfLb1ELb1EEE, `hard` a run-time value) is walked by TNNTNTNNTTTN.
-DEFAULT_TABLE = "TNTNTNTTTN"
+#    1  N  the early exit (some flag not 0, or not |theta| < 1e5): no lane
+#    2  N  the compiler's own test that the early exit was not taken (it keeps the two arms of that branch as a flag)
+#    3  N  the solve: some row of the wave is violated at u_box
+#    4  N  the late exit (a row without nn > 0, a flat direction, a parallel partner): no lane
+#    5  N  the store of u and status: lane 0 of every group
+# The listing of the commit before (ten branches, six of them taken around cold blocks) is walked by TNTNTNTTTN.
+DEFAULT_TABLE = "NNNNN"
 
 CLASSES = ("vector", "dpp", "salu", "nop", "control", "memory")
 
@@ -115,6 +112,7 @@ def sets_condition(mn, txt):
 def walk(body, table, trace=False):
     labels = {lab: n for n, (_, lab, _, _) in enumerate(body) if lab}
     counts = dict.fromkeys(CLASSES, 0)
+    taken = 0                                   # taken branches on the path, conditional or not: each is an instruction-fetch redirect
     pc, used, last_cond, steps = 0, 0, "", 0
     while True:
         steps += 1
@@ -132,6 +130,7 @@ def walk(body, table, trace=False):
             last_cond = f"{line}: {txt}"
         if mn == "s_branch":
             pc = labels[txt.split()[1]]
+            taken += 1
         elif mn.startswith("s_cbranch"):
             if used >= len(table):
                 raise SystemExit(f"the table ends before the walk does: branch {used + 1} at line {line}: {txt}   (after {last_cond})")
@@ -141,9 +140,10 @@ def walk(body, table, trace=False):
                 print(f"  branch {used:2d}  line {line:5d}  {txt:34s} {'taken' if take else 'falls through':14s} after {last_cond}")
             if take:
                 pc = labels[txt.split()[1]]
+                taken += 1
     if used != len(table):
         raise SystemExit(f"the walk met {used} conditional branches, the table has {len(table)}")
-    return counts
+    return counts, taken
 
 
 def main():
@@ -157,12 +157,13 @@ def main():
         raise SystemExit("the table is a string of T and N")
     text = open(a.asm).read() if a.asm else build_asm()
     body = kernel_body(text, a.kernel)
-    counts = walk(body, a.table, a.trace)
+    counts, taken = walk(body, a.table, a.trace)
     static = sum(1 for _, lab, _, _ in body if not lab)
     print(f"kernel *{a.kernel}*: {static} instructions in the listing, table {a.table}")
     for c in CLASSES:
         print(f"  {c:8s} {counts[c]:4d}")
     print(f"  {'total':8s} {sum(counts.values()):4d}")
+    print(f"  taken branches on the path: {taken} (the s_branch of the kernel-argument preload prologue included)")
 
 
 if __name__ == "__main__":

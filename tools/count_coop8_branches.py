@@ -1,20 +1,20 @@
 #!/usr/bin/env python3
-"""How many waves of a DynamicUnicycle2D CBF-QP batch take the cold branches of cbfqp_coop8_du_kernel.
+"""How many waves of a DynamicUnicycle2D CBF-QP batch leave the fast path of cbfqp_coop8_du_kernel, and why.
 
 CPU only.  The rows come from oracle/cbf_qp.assemble_rows on the storage-rounded (f32) inputs, are normalised as the kernel
-normalises them, and are grouped as the kernel groups them: 8 agents of 8 rows per wave.  A wave that enters the solve (some row
-violated at u_box = clamp(u_ref)) takes
-  * the flat-direction block of clip_box_tol_lazy when a unit normal of ANY of its rows has a component that is exactly 0.0,
-  * the parallel-partner block of coop_solve_all8_full when two rows of one agent have |n_i x n_j| <= eps_par (1e-12),
-  * the bad-obstacle block of the tail when a row's flag is neither 0 nor 1 (that one in every wave, entering the solve or not),
-  * the select of normalise_row_as_generic when some row has not nn > 0 -- an all-zero row, a normal whose squares underflow, a
-    NaN, a bad row (the kernel zeroes it) -- in every wave, entering the solve or not.
-The parallel-partner flag of the kernel is ballot(min over the seven partners of |a| <= eps_par), a = n_partner . d_line, which is
-|n_i x n_j| of the unit normals: the same set of waves as the per-partner flags it replaced.  A wave-uniform test on "any flag
-other than 0 in the wave" (the dispatch of cbf_row) is counted as well; the kernel does not branch on it.
-The oracle's rows differ from the kernel's in the last bits (its sincos is the C library's), so a pair that sits within a few ulp
-of eps_par could be counted differently; the smallest |n_i x n_j| and the smallest |component| of the batch are printed so that the
-distance to the thresholds can be seen.
+normalises them, and are grouped as the kernel groups them: 8 agents of 8 rows per wave.  The kernel's fast path takes every lane
+as ordinary; a wave leaves it for the generic K = 8 sequence
+  * through the early exit when some row's flag is not 0 (a superellipsoid, or a flag that is neither 0 nor 1: the bad obstacle)
+    or some agent has not |theta| < 1e5,
+  * through the late exit when some row has not nn > 0 -- an all-zero row, a normal whose squares underflow, a NaN (in every wave,
+    entering the solve or not) -- or, in a wave that enters the solve (some row violated at u_box = clamp(u_ref)), when a unit
+    normal of ANY of its rows has a component that is exactly 0.0 (a flat direction of the box clip) or two rows of one agent have
+    |n_i x n_j| <= eps_par (1e-12: a parallel partner).
+The parallel-partner flag of the kernel is min over the seven partners of |a| <= eps_par, a = n_partner . d_line, which is
+|n_i x n_j| of the unit normals.  The oracle's rows differ from the kernel's in the last bits (its sincos is the C library's), so
+a pair that sits within a few ulp of eps_par could be counted differently; the smallest |n_i x n_j| and the smallest |component|
+of the batch are printed so that the distance to the thresholds can be seen.  tests/test_cbfqp_straight_path.py asserts that the
+benchmark batch meets none of the conditions.
 
 usage: count_coop8_branches.py [--agents 4096] [--seed 0]
 """
@@ -85,6 +85,7 @@ def main():
     X, u_ref, obs = f32(X), f32(u_ref), f32(obs)
     spec = R.default_spec(R.MODEL_DU); spec.update(a_max=1.0, w_max=0.5, radius=0.25)
     c = conditions(X, u_ref, obs, spec)
+    big_theta = ~(np.abs(X[:, 2]) < 1.0e5)
     pad = (-a.agents) % 8
     wave = lambda m: np.concatenate([m, np.zeros(pad, dtype=bool)]).reshape(-1, 8).any(axis=1)
     enters = wave(c["viol"].any(axis=1))
@@ -96,11 +97,12 @@ def main():
     nv = c["viol"].sum(axis=1)
     print(f"{len(enters)} waves, {int(enters.sum())} enter the solve; violated rows per agent: max {int(nv.max())}, "
           f"{int((nv >= 2).sum())} agents with two or more")
-    print(f"waves that take the flat-direction block: {int(flat.sum())}   (smallest |component| of a unit normal: {c['min_comp']:.3e})")
-    print(f"waves that take the parallel-partner block: {int(par.sum())}   (smallest |n_i x n_j|: {c['min_cross']:.3e}, threshold {EPS_PAR:g})")
-    print(f"waves that take the bad-obstacle block: {int(bad.sum())}")
-    print(f"waves with a row that has not nn > 0 (the select of the normalisation): {int(degenerate.sum())}")
-    print(f"waves that hold a flag other than 0 (not branched on): {int(noncircle.sum())}")
+    print(f"waves with a flat direction (late exit): {int(flat.sum())}   (smallest |component| of a unit normal: {c['min_comp']:.3e})")
+    print(f"waves with a parallel partner (late exit): {int(par.sum())}   (smallest |n_i x n_j|: {c['min_cross']:.3e}, threshold {EPS_PAR:g})")
+    print(f"waves with a bad obstacle (early exit, a flag that is not 0): {int(bad.sum())}")
+    print(f"waves with a row that has not nn > 0 (late exit): {int(degenerate.sum())}")
+    print(f"waves that hold a flag other than 0 (early exit): {int(noncircle.sum())}")
+    print(f"waves that hold an agent without |theta| < 1e5 (early exit): {int(wave(big_theta).sum())}")
 
 
 if __name__ == "__main__":
