@@ -65,6 +65,9 @@ __device__ __forceinline__ OdRow<TC> od_build_row(const Agent<TC>& ag, const TC*
         TC d[4];
         if constexpr (MODEL == SC_MODEL_KINEMATIC_BICYCLE2D_C3BF) c3bf(ag, o, k.R, h, d);
         else dpcbf(ag, o, k.R, h, d);
+        // the reference's max(|p|^2 - ego^2, eps) hands a NaN radius on (kinematic_bicycle2D_c3bf.py:15-75); fmax_ in c3bf() drops it
+        // and leaves a finite row.  An infinite radius gives eps there and here alike
+        if (o[2] != o[2]) h = num<TC>::nan();
         a0 = d[3];
         a1 = -ag.f1 * d[0] + ag.f0 * d[1] + ag.v * k.inv_Lr * d[2];
         b = d[0] * ag.f0 + d[1] * ag.f1;

@@ -109,9 +109,9 @@ class OdTrackingOracle(TrackingOracle):
         nearest = None if self.nearest_multi_obs is None else self.nearest_multi_obs[0]      # tracking.py:585-586
         r = OD.solve(m, self.X, u_ref, nearest, self.spec, self.od_param)
         self.status = r["status"]
-        # with an obstacle and h != 0 the decay variable alone can satisfy the row, so the QP has a solution; the enumeration of
-        # oracle/od_cbf_qp.py still reports 'infeasible' when its determinant test skips the nearly singular active set of the row and
-        # both input bounds.  Such a step is outside the oracle's range of validity: it is counted, and the scenes are seeded to have none
+        # with an obstacle and h != 0 the decay variable alone can satisfy the row, so the QP has a solution.  An 'infeasible' from the
+        # enumeration of oracle/od_cbf_qp.py would then be the oracle's own failure (its determinant test once skipped the nearly
+        # singular active set of the row and both input bounds).  Such a step is counted, and the GPU tests assert there is none
         if self.status != STATUS_OPTIMAL and nearest is not None and np.isfinite(r["h"]) and r["h"] != 0.0 and np.all(np.isfinite(u_ref)):
             self.n_rejected_feasible += 1
         if nearest is not None:

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from oracle import od_cbf_qp as OD, robots as R
+import _od_qp_cases as C
 import _od_tracking_oracle as O
 
 SM = O.SM_INDEX
@@ -67,21 +68,25 @@ def test_selection_margin_flags_ties():
 
 def test_where_the_enumeration_oracle_ends():
     """A DPCBF step recorded from the moving-obstacle scene (seed 0, agent 60, step 14): the row cannot be met by the inputs, so the
-    optimum has the row and both input bounds active and a large decay.  The QP has feasible points (the decay variable alone
-    satisfies the row), yet the oracle's determinant test, scaled by |K|max^3 ~ (A1^2 / 2)^3, skips that nearly singular active set
-    and reports 'infeasible'.  OdTrackingOracle counts such steps (n_rejected_feasible) and the GPU scenes are seeded to have none."""
+    optimum has the row and both input bounds active and a large decay.  The oracle used to report this QP 'infeasible': its
+    determinant test was scaled by |K|max^3 ~ (A1^2 / 2)^3 and skipped that nearly singular active set.  It now eliminates the inputs
+    held at a bound and tests singularity free of scale, so it returns the optimum, and the certificate of tests/_od_qp_cases.py
+    (which enumerates nothing) accepts it -- also under the default penalty 1e4, where the decay's share of the row is ~1e-10."""
     A, b, e1 = np.array([-0.34224332, -195.33207949]), -68.72046349533927, -0.17231294715026504
     u_ref, lo, hi = np.array([-0.15936608, 0.30282535]), np.array([-5.0, -0.30282535497070506]), np.array([5.0, 0.30282535497070506])
-    D, r = np.array([1.0, 1.0, 1.0]), np.array([u_ref[0], u_ref[1], 1.0])
     G = np.array([[A[0], A[1], e1], [1, 0, 0], [-1, 0, 0], [0, 1, 0], [0, -1, 0]], dtype=np.float64)
     c = np.array([b, -lo[0], hi[0], -lo[1], hi[1]])
-    u = np.clip(u_ref, lo, hi)
-    x = np.array([u[0], u[1], -(A @ u + b) / e1 - 1.0])               # a feasible point: inside the box, the row slack (e1 < 0)
-    assert np.all(G @ x + c >= 0.0)
-    assert OD.solve_diag_qp(D, r, G, c)[1] == OD.STATUS_INFEASIBLE
-    # the optimum by hand: u at (lo0, lo1), omega1 from the active row; cheaper than x, and its multipliers are non-negative
-    xs = np.array([lo[0], lo[1], -(A @ lo + b) / e1])
-    lam = 2.0 * D[2] * (xs[2] - r[2]) / e1
-    assert lam > 0 and abs(G[0] @ xs + c[0]) < 1e-9
-    assert 2 * (xs[0] - r[0]) - lam * A[0] >= 0 and 2 * (xs[1] - r[1]) - lam * A[1] >= 0        # bound multipliers at lo0, lo1
-    assert np.sum(D * (xs - r) ** 2) < np.sum(D * (x - r) ** 2)
+    for p1 in (1.0, 1e4):
+        D, r = np.array([1.0, 1.0, p1]), np.array([u_ref[0], u_ref[1], 1.0])
+        # the optimum by hand: u at (lo0, lo1), omega1 from the active row; its multipliers are non-negative
+        xs = np.array([lo[0], lo[1], -(A @ lo + b) / e1])
+        lam = 2.0 * D[2] * (xs[2] - r[2]) / e1
+        assert lam > 0 and abs(G[0] @ xs + c[0]) < 1e-9
+        assert 2 * (xs[0] - r[0]) - lam * A[0] >= 0 and 2 * (xs[1] - r[1]) - lam * A[1] >= 0    # bound multipliers at lo0, lo1
+        x, st = OD.solve_diag_qp(D, r, G, c)
+        assert st == OD.STATUS_OPTIMAL
+        np.testing.assert_allclose(x, xs, rtol=1e-12, atol=0)
+        cert = C.certificate(D, r, G, c, x)
+        assert list(cert["active"]) == [True, True, False, True, False] and cert["mu"].min() >= 0
+        assert C.accepts(cert, x, 1e-10), cert
+        assert C.classify(D, r, G, c, x) == "act/lo/lo"

@@ -29,12 +29,12 @@ RUNS = {
 }
 # The seeds were chosen on the CPU, from the oracle alone, by two counts that every parity test asserts again: no agent within TIE of a
 # selection tie, and no step on which oracle/od_cbf_qp.py reports 'infeasible' for a QP that has a solution by construction (an
-# obstacle with h != 0: the decay variable alone satisfies the row).  The second happens to the DPCBF bicycle when the row and both
-# input bounds are active: its steering coefficient is ~1e2, the oracle's determinant test (scaled by |K|max^3) then skips that nearly
-# singular active set and finds no other (tests/test_oracle_od_tracking.py pins one such QP).  The kernel returns the optimum there
-# (|omega1| ~ 1e2 .. 1e4), so on such a step the two part ways (the oracle ends the agent with -2, the kernel drives on) and the
-# loop cannot be held to this oracle there.  DPCBF scenes of this generator: seeds 0 .. 30 have 0 .. 11 such
-# steps among 136 agents x 100 steps; 5, 7, 13 and 17 have none, and 17 has the most agents ending in -2 (42, all collisions).
+# obstacle with h != 0: the decay variable alone satisfies the row).  The second used to happen to the DPCBF bicycle when the row and
+# both input bounds are active: its steering coefficient is ~1e2, and the oracle's determinant test, then scaled by |K|max^3, skipped
+# that nearly singular active set and found no other; seeds 0 .. 30 of this generator had 0 .. 11 such steps among 136 agents x 100
+# steps, and 5, 7, 13 and 17 had none.  The oracle now eliminates the inputs held at a bound and tests singularity free of scale
+# (tests/test_oracle_od_tracking.py pins one such QP, tests/test_od_qp_cases.py holds it to a certificate on that whole class), so the
+# count can only have fallen and stays asserted as a guard.  Seed 17 is kept: it has the most agents ending in -2 (42, all collisions).
 
 
 def setup(name, io="f64", B_=B):
