@@ -23,35 +23,43 @@ def default_spec():
     return dict(w_max=2.0, Kp=3.0, radius=0.25, base_pos=(0.0, 0.0))
 
 
-def link_steps():
+def _links(link_lengths):
+    """The three link lengths as float64; ``None`` is the reference's constant."""
+    return LINK_LENGTHS if link_lengths is None else np.asarray(link_lengths, dtype=np.float64).reshape(3)
+
+
+def link_steps(link_lengths=None):
     """Circles per link minus one: ``int(np.ceil(link_dist / step_len))`` evaluated in float64 (manipulator2D.py:143)."""
-    return [int(np.ceil(L / STEP_LEN)) for L in LINK_LENGTHS]
+    return [int(np.ceil(L / STEP_LEN)) for L in _links(link_lengths)]
 
 
-def joint_positions(X, base=(0.0, 0.0)):
+def joint_positions(X, base=(0.0, 0.0), link_lengths=None):
     """Base, joint 1, joint 2, end effector (manipulator2D.py:52-60)."""
+    LL = _links(link_lengths)
     P = [np.array(base, dtype=np.float64)]
     ang = 0.0
     for i in range(3):
         ang += X[i]
-        P.append(P[-1] + LINK_LENGTHS[i] * np.array([math.cos(ang), math.sin(ang)]))
+        P.append(P[-1] + LL[i] * np.array([math.cos(ang), math.sin(ang)]))
     return P
 
 
-def end_effector(X, base=(0.0, 0.0)):
+def end_effector(X, base=(0.0, 0.0), link_lengths=None):
     """manipulator2D.py:42-50 (accumulates x and y separately from the base)."""
+    LL = _links(link_lengths)
     x, y = float(base[0]), float(base[1])
     ang = 0.0
     for i in range(3):
         ang += X[i]
-        x += LINK_LENGTHS[i] * math.cos(ang)
-        y += LINK_LENGTHS[i] * math.sin(ang)
+        x += LL[i] * math.cos(ang)
+        y += LL[i] * math.sin(ang)
     return np.array([x, y])
 
 
-def jacobian(X):
+def jacobian(X, link_lengths=None):
     """End-effector Jacobian (2x3), manipulator2D.py:62-108: column i = sum over links k >= i of
     l_k (-sin, cos)(theta_1 + .. + theta_k)."""
+    LL = _links(link_lengths)
     J = np.zeros((2, 3))
     for i in range(3):
         ang = 0.0
@@ -60,8 +68,8 @@ def jacobian(X):
         jx = jy = 0.0
         for k in range(i, 3):
             ang += X[k]
-            jx -= LINK_LENGTHS[k] * math.sin(ang)
-            jy += LINK_LENGTHS[k] * math.cos(ang)
+            jx -= LL[k] * math.sin(ang)
+            jy += LL[k] * math.cos(ang)
         J[0, i], J[1, i] = jx, jy
     return J
 
@@ -78,24 +86,25 @@ def step(X, U, dt):
     return np.asarray(X, dtype=np.float64) + np.asarray(U, dtype=np.float64) * dt     # manipulator2D.py:38-41 (no wrap)
 
 
-def nominal_input(X, goal, spec, base=(0.0, 0.0)):
+def nominal_input(X, goal, spec, base=(0.0, 0.0), link_lengths=None):
     """Jacobian-transpose control clipped to w_max (manipulator2D.py:110-127)."""
-    err = np.asarray(goal, dtype=np.float64)[:2] - end_effector(X, base)
-    w = jacobian(X).T @ (spec["Kp"] * err)
+    err = np.asarray(goal, dtype=np.float64)[:2] - end_effector(X, base, link_lengths)
+    w = jacobian(X, link_lengths).T @ (spec["Kp"] * err)
     return np.clip(w, -spec["w_max"], spec["w_max"])
 
 
-def link_circles(X, base=(0.0, 0.0)):
+def link_circles(X, base=(0.0, 0.0), link_lengths=None):
     """Centres and link index of the discretised links (manipulator2D.py:129-152): per link ``ns + 1`` points at
     ``p_start + (j / ns) (dx, dy)``."""
+    LL = _links(link_lengths)
     out = []
     p_start = np.array(base, dtype=np.float64)
     ang = 0.0
     for i in range(3):
         ang += X[i]
-        d = np.array([LINK_LENGTHS[i] * math.cos(ang), LINK_LENGTHS[i] * math.sin(ang)])
+        d = np.array([LL[i] * math.cos(ang), LL[i] * math.sin(ang)])
         p_end = p_start + d
-        ns = int(np.ceil(LINK_LENGTHS[i] / STEP_LEN))
+        ns = int(np.ceil(LL[i] / STEP_LEN))
         for j in range(ns + 1):
             t = j / ns
             out.append((p_start + t * d, i))
@@ -103,33 +112,34 @@ def link_circles(X, base=(0.0, 0.0)):
     return out
 
 
-def point_jacobian(X, pt, link_idx, base=(0.0, 0.0)):
+def point_jacobian(X, pt, link_idx, base=(0.0, 0.0), link_lengths=None):
     """manipulator2D.py:154-182: J[:, k] = z x (pt - P_k) for k <= link_idx, zero beyond."""
+    LL = _links(link_lengths)
     J = np.zeros((2, 3))
     P = [np.array(base, dtype=np.float64)]
     ang = 0.0
     for i in range(link_idx + 1):
         if i > 0:
             ang += X[i - 1]
-            P.append(P[-1] + LINK_LENGTHS[i - 1] * np.array([math.cos(ang), math.sin(ang)]))
+            P.append(P[-1] + LL[i - 1] * np.array([math.cos(ang), math.sin(ang)]))
     for k in range(link_idx + 1):
         J[0, k] = -(pt[1] - P[k][1])
         J[1, k] = pt[0] - P[k][0]
     return J
 
 
-def agent_barrier(X, obs, R, beta=BETA, base=(0.0, 0.0)):
+def agent_barrier(X, obs, R, beta=BETA, base=(0.0, 0.0), link_lengths=None):
     """manipulator2D.py:185-224: one (h, dh/dq) per link circle: h = |c - o|^2 - beta (R + r)^2, dh = 2 (c - o) J_c."""
     hs, dhs = [], []
-    for c, li in link_circles(X, base):
+    for c, li in link_circles(X, base, link_lengths):
         dx, dy = c[0] - obs[0], c[1] - obs[1]
         d_min = R + obs[2]
         hs.append(dx * dx + dy * dy - beta * d_min ** 2)
-        dhs.append(2.0 * np.array([dx, dy]) @ point_jacobian(X, c, li, base))
+        dhs.append(2.0 * np.array([dx, dy]) @ point_jacobian(X, c, li, base, link_lengths))
     return hs, dhs
 
 
-def assemble_rows(X, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode="cbf", base=(0.0, 0.0)):
+def assemble_rows(X, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode="cbf", base=(0.0, 0.0), link_lengths=None):
     """cbf_qp.py:110-151: zeroed A1 (num_rows, 3) / b1; obstacles in order, circles in order, stop at num_rows."""
     A = np.zeros((num_rows, 3))
     b = np.zeros(num_rows)
@@ -140,7 +150,7 @@ def assemble_rows(X, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode=
             continue
         if row >= num_rows:
             break
-        hs, dhs = agent_barrier(X, np.asarray(obs, dtype=np.float64), spec["radius"], base=base)
+        hs, dhs = agent_barrier(X, np.asarray(obs, dtype=np.float64), spec["radius"], base=base, link_lengths=link_lengths)
         for h, dh in zip(hs, dhs):
             if row >= num_rows:
                 break
@@ -151,12 +161,12 @@ def assemble_rows(X, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode=
     return A, b, hv
 
 
-def solve(X, u_ref, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode="cbf", base=(0.0, 0.0)):
+def solve(X, u_ref, obs_list, spec, alpha=1.0, num_rows=150, dt=0.05, cbf_mode="cbf", base=(0.0, 0.0), link_lengths=None):
     """One Manipulator2D CBF-QP solve; dict(u, status, h, A, b).  ``obs_list is None`` -> u_ref (cbf_qp.py:113-118)."""
     u_ref = np.asarray(u_ref, dtype=np.float64).reshape(3)
     if obs_list is None:
         return dict(u=u_ref.copy(), status=STATUS_OPTIMAL, h=np.full(num_rows, np.nan), A=np.zeros((num_rows, 3)), b=np.zeros(num_rows))
-    A, b, hv = assemble_rows(X, obs_list, spec, alpha, num_rows, dt, cbf_mode, base)
+    A, b, hv = assemble_rows(X, obs_list, spec, alpha, num_rows, dt, cbf_mode, base, link_lengths)
     w = spec["w_max"]
     Gb = np.vstack([np.eye(3), -np.eye(3)])
     u, status = solve_qpn(np.vstack([A, Gb]), np.concatenate([b, np.full(6, w)]), u_ref)
@@ -169,7 +179,8 @@ class ArmTrackingOracle:
     stays 0 (robots/robot.py:139-148) and its "position" is the fixed base (:354-356), which is what the obstacle ranking,
     the field-of-view test and the collision test see."""
 
-    def __init__(self, q0, spec, base=(0.0, 0.0), dt=0.05, obs=None, num_constraints=150, enable_rotation=True, alpha=1.0):
+    def __init__(self, q0, spec, base=(0.0, 0.0), dt=0.05, obs=None, num_constraints=150, enable_rotation=True, alpha=1.0,
+                 link_lengths=None):
         self.spec = dict(default_spec()); self.spec.update(spec)
         self.base = np.asarray(base, dtype=np.float64)
         self.dt = dt
@@ -178,6 +189,7 @@ class ArmTrackingOracle:
         self.num_constraints = num_constraints
         self.enable_rotation = enable_rotation
         self.alpha = alpha
+        self.link_lengths = link_lengths
         self.reached_threshold = self.spec.get("reached_threshold", 0.3)
         self.rotation_threshold = 0.1
         self.fov_angle = math.radians(float(self.spec.get("fov_angle", 70.0)))
@@ -190,7 +202,7 @@ class ArmTrackingOracle:
     def set_waypoints(self, waypoints):
         wp = np.array(waypoints, dtype=np.float64)
         if len(wp) >= 2:                                    # filter_waypoints with the end effector as the robot position
-            aug = np.vstack((end_effector(self.X, self.base), wp[:, :2]))
+            aug = np.vstack((end_effector(self.X, self.base, self.link_lengths), wp[:, :2]))
             dist = np.linalg.norm(np.diff(aug, axis=0), axis=1)
             wp = aug[np.concatenate(([False], dist >= self.reached_threshold))]
         self.waypoints = wp
@@ -215,7 +227,7 @@ class ArmTrackingOracle:
         if self.current_goal_index >= len(self.waypoints):
             return None
         wp = self.waypoints[self.current_goal_index]
-        if np.linalg.norm(end_effector(self.X, self.base) - wp[:2]) < self.reached_threshold:
+        if np.linalg.norm(end_effector(self.X, self.base, self.link_lengths) - wp[:2]) < self.reached_threshold:
             self.current_goal_index += 1
             if self.current_goal_index >= len(self.waypoints):
                 self.state_machine = "idle"
@@ -235,9 +247,9 @@ class ArmTrackingOracle:
         else:
             self.goal = self.update_goal()
         near = self.ranked_obstacles()
-        u_ref = np.zeros(3) if self.goal is None else nominal_input(self.X, self.goal, self.spec, self.base)
+        u_ref = np.zeros(3) if self.goal is None else nominal_input(self.X, self.goal, self.spec, self.base, self.link_lengths)
         r = solve(self.X, u_ref, None if near is None else list(near), self.spec, self.alpha, self.num_constraints, self.dt,
-                  "cbf", self.base)
+                  "cbf", self.base, self.link_lengths)
         self.status = r["status"]
         collide = bool(len(self.obs)) and bool(np.any(np.linalg.norm(self.obs[:, :2] - self.base[None, :], axis=1)
                                                       < self.obs[:, 2] + self.spec["radius"]))

@@ -200,6 +200,8 @@ __device__ __forceinline__ int manip_qp(const sc_manip_cbfqp_params& p, const do
         }
         if (r >= Rr && r < p.num_rows) puth(r, 0.0);
     }
+    // RPL follows the rows K obstacles can fill, so with few obstacles the slots end before num_rows: the rest of h is unused too
+    for (int r = lane + 64 * RPL; r < p.num_rows; r += 64) puth(r, 0.0);
 
     u[0] = ur0; u[1] = ur1; u[2] = ur2;
     if (!(finite_(u[0]) && finite_(u[1]) && finite_(u[2]))) dead = true;

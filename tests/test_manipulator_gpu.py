@@ -42,10 +42,11 @@ def test_golden_cases_one_launch(mode):
     torch.cuda.synchronize()
     u, st, h = u.cpu().numpy(), st.cpu().numpy(), h.cpu().numpy()
     so = G[f"{mode}/status_oracle"]
-    n_checked = 0
+    n_checked = n_excused = 0
     for i in range(n):
         if st[i] != so[i]:
             assert abs(margin(G[f"{mode}/A"][i], G[f"{mode}/b"][i], W_MAX)) < 1e-6, f"status differs at case {i}"
+            n_excused += 1
             continue
         rows = min(NR, int(k[i]) * 25)
         gain = 1.0 if mode == "cbf" else 1.0 / DT
@@ -57,6 +58,7 @@ def test_golden_cases_one_launch(mode):
         else:
             assert np.all(np.isnan(u[i]))
     assert n_checked > n // 2
+    assert n_excused <= n // 100, f"{n_excused} status differences excused"          # at most 1 % (no golden case is that close)
 
 
 def random_batch(B, K, seed, touching=0.15):
@@ -81,13 +83,14 @@ def test_random_batch_matches_oracle(K, num_rows):
     u, st, h = ctl.solve(t(X), t(ur), t(obs))
     torch.cuda.synchronize()
     u, st, h = u.cpu().numpy(), st.cpu().numpy(), h.cpu().numpy()
-    n_opt = n_inf = n_act = 0
+    n_opt = n_inf = n_act = n_excused = 0
     for i in range(B):
         r = M.solve(X[i], ur[i], list(obs[i]), SPEC, 1.0, num_rows, 0.05, "cbf", BASE)
         rows = min(num_rows, K * 25)
         np.testing.assert_allclose(h[i, :rows], r["h"][:rows], rtol=0, atol=1e-9)
         if st[i] != r["status"]:
             assert abs(margin(r["A"], r["b"], W_MAX)) < 1e-6, f"status differs at agent {i}"
+            n_excused += 1
             continue
         if r["status"] == 0:
             assert np.abs(u[i] - r["u"]).max() <= 1e-7, f"agent {i}"
@@ -96,6 +99,7 @@ def test_random_batch_matches_oracle(K, num_rows):
         else:
             n_inf += 1
     assert n_opt > B // 2 and n_act > 10
+    assert n_excused <= B // 100, f"{n_excused} status differences excused"          # at most 1 % (the oracle has none that close)
     assert set(np.unique(st)) <= {0, 1}
 
 
@@ -110,17 +114,19 @@ def test_f32_arrays_and_shared_table_and_counts():
                          torch.tensor(n_obs, dtype=torch.int32, device=DEV))
     torch.cuda.synchronize()
     u, st = u.double().cpu().numpy(), st.cpu().numpy()
-    n = 0
+    n = n_excused = 0
     for i in range(B):
         ol = list(sh32.astype(np.float64)[: n_obs[i]])
         r = M.solve(X32[i].astype(np.float64), ur32[i].astype(np.float64), ol, SPEC, 1.0, 150, 0.05, "cbf", BASE)
         if st[i] != r["status"]:
             assert abs(margin(r["A"], r["b"], W_MAX)) < 1e-5
+            n_excused += 1
             continue
         if r["status"] == 0:
             assert np.abs(u[i] - r["u"]).max() <= 2e-6 * max(1.0, np.abs(r["u"]).max())
             n += 1
     assert n > B // 2
+    assert n_excused <= B // 100, f"{n_excused} status differences excused"          # at most 1 % (the oracle has none that close)
 
 
 def test_drop_in_class_single_arm():
