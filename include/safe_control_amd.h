@@ -902,6 +902,40 @@ int sc_tracking_sense_rollout_batch(const sc_tracking_params* params, const sc_s
                                     int32_t* ret, int32_t* ret_step, void* traj_X, void* traj_U, void* traj_yaw,
                                     int64_t* traj_seen, void* stream);
 
+/* The sensing loop's control_step split around the solve, for position controllers that are their own launch (MPC-CBF, the
+ * default of examples/test_unknown_env.py): sc_tracking_select_batch / sc_tracking_apply_batch with the camera cone, the unknown
+ * table, the memory of sighted rows and the integrators' yaw / u_att.  One control step per call pair; params->n_steps is not read.
+ *   sc_tracking_sense_select_batch = tracking.py:569-609.  For an agent with ret == 0: the state machine / goal update of the fused
+ *     kernel (heading = yaw for the integrators; leaving 'rotate' sets u_att to NaN), 'fov' detection over all n_unknown rows,
+ *     seen = persistent ? seen | now : now, then the nearest-unpassed selection over the known rows followed by the remembered
+ *     unknown rows (stable in distance, the fused kernel's use_all rule).  obs_out [B,K,7]: known rows as they are (superellipsoids
+ *     included), a remembered unknown row as [x, y, r, 0, 0, 0, 0] with the radius it was sighted at, missing rows
+ *     [1000, 1000, 0, 0, 0, 0, 0] (MPCCBF.update_tvp, mpc_cbf.py:338-364).  u_ref_out [B,2] (tracking.py:589-604): a rotating
+ *     integrator in 'rotate' gets u_att = clip(2 wrap(goal_angle - yaw), +-w_max) and u_ref = stop().  goal_out [B,2] and
+ *     track_out [B] as in sc_tracking_select_batch.  An agent with ret != 0 keeps its state machine, goal, seen and u_att; its
+ *     outputs are written from them with track_out = 0.  yaw is read only.
+ *   sc_tracking_sense_apply_batch = tracking.py:620-668.  In 'track' with a rotating integrator u_att comes from the attitude
+ *     controller, from the applied u and the pre-step state; the pre-step and post-step collision tests run against the known table
+ *     and against EVERY unknown row as the circle of radius o[2]; then robot.step(u) and yaw = wrap(yaw + u_att dt) unless u_att is
+ *     NaN (for DynamicUnicycle2D yaw, when given, receives X[2]).  u_status [B] (SC_STATUS_*) or NULL when the controller never
+ *     reports failure (mpc_cbf.py:10); return codes and ret_step as in sc_tracking_apply_batch.
+ * Checked as sc_tracking_sense_rollout_batch checks them: the three models (others SC_ERR_UNSUPPORTED), n_unknown, the camera and
+ * w_max finite and > 0, att_type against the model and enable_rotation, yaw / u_att NULL only for DynamicUnicycle2D or a
+ * non-rotating integrator, dyn_obs = 0, num_constraints <= 16, unknown_table with n_unknown > 0, seen (select); a NULL array with
+ * B > 0 is SC_ERR_INVALID_ARGUMENT.  B = 0 returns after the checks without a launch. */
+int sc_tracking_sense_select_batch(const sc_tracking_params* params, const sc_sense_params* sense,
+                                   int64_t B, int32_t M, const void* X, const void* waypoints, const int32_t* n_wp,
+                                   int32_t* wp_index, int32_t* state_machine, void* goal, const void* obs_table,
+                                   const void* unknown_table, int64_t* seen, const void* yaw, void* u_att,
+                                   const int32_t* ret, void* obs_out, void* goal_out, void* u_ref_out,
+                                   int32_t* track_out, void* stream);
+
+int sc_tracking_sense_apply_batch(const sc_tracking_params* params, const sc_sense_params* sense,
+                                  int64_t B, int32_t M, int32_t step_index, void* X, const int32_t* state_machine,
+                                  const void* goal, const void* obs_table, const void* unknown_table, void* yaw,
+                                  void* u_att, const void* u, const int32_t* u_status, void* u_last,
+                                  int32_t* ret, int32_t* ret_step, void* stream);
+
 /* Closed loop for the arm (SURVEY 8f-1 for Manipulator2D): `n_steps` iterations of LocalTrackingController.control_step
  * (tracking.py:559-668; goal_reached on the end effector :263-268; update_goal :497-535) with nominal_input / step of
  * robots/manipulator2D.py:38-41,110-127 and the CBF-QP above, one arm per wavefront, joint angles in registers.

@@ -22,5 +22,6 @@ from .position_control.optimal_decay_mpc_cbf_gn import OptimalDecayGnMPCCBF, Bat
 from .shielding import MPS, BatchedShield, Gatekeeper  # noqa: F401
 from .robots.spec import RobotHandle, complete_robot_spec  # noqa: F401
 from .tracking import BatchedTrackingController, BatchedFleetTrackingController, BatchedSensingTrackingController  # noqa: F401
+from .tracking import BatchedSensingMPCTrackingController  # noqa: F401
 
 __version__ = "0.1.0"

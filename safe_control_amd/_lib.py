@@ -443,6 +443,10 @@ SYMBOLS = {
                                      + [C.c_void_p] * 15),
     "sc_tracking_sense_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.POINTER(SenseParams), C.c_int64, C.c_int32]
                                         + [C.c_void_p] * 19),
+    "sc_tracking_sense_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.POINTER(SenseParams), C.c_int64, C.c_int32]
+                                       + [C.c_void_p] * 17),
+    "sc_tracking_sense_apply_batch": (C.c_int, [C.POINTER(TrackingParams), C.POINTER(SenseParams), C.c_int64, C.c_int32, C.c_int32]
+                                      + [C.c_void_p] * 13),
     "sc_mpccbf_solve_batch_host": (C.c_int, [C.POINTER(MpcCbfParams), C.c_int64, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_int]),

@@ -53,6 +53,14 @@ hipError_t tracking_sense_launch(const sc_tracking_params& p, const sc_sense_par
                                  const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const void* utable,
                                  long long* seen, void* yaw, void* u_att, void* u_last, int* ret, int* ret_step, void* tX, void* tU,
                                  void* tYaw, long long* tSeen, hipStream_t stream);
+hipError_t tracking_sense_select_launch(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, const void* X,
+                                        const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
+                                        const void* utable, long long* seen, const void* yaw, void* u_att, const int* ret,
+                                        void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream);
+hipError_t tracking_sense_apply_launch(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, int step_index,
+                                       void* X, const int* sm, const void* goal, const void* table, const void* utable, void* yaw,
+                                       void* u_att, const void* u, const int* u_status, void* u_last, int* ret, int* ret_step,
+                                       hipStream_t stream);
 
 hipError_t manip_cbfqp_launch(const sc_manip_cbfqp_params& p, long long B, int K, const void* X, const void* u_ref,
                               const void* obs, const int* n_obs, void* u_out, int* status, void* h_out, hipStream_t stream);
@@ -1610,6 +1618,78 @@ int sc_tracking_sense_rollout_batch(const sc_tracking_params* params, const sc_s
                                              obs_table, unknown_table, (long long*)seen, yaw, u_att, u_last, ret, ret_step, traj_X,
                                              traj_U, traj_yaw, (long long*)traj_seen, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "tracking sense kernel launch");
+    return SC_OK;
+}
+
+// what sc_tracking_sense_select_batch and sc_tracking_sense_apply_batch check of their parameters and of the arrays they share: the
+// checks of sc_tracking_sense_rollout_batch, without n_steps (one step per call)
+static int check_sense_split(const sc_tracking_params* params, const sc_sense_params* sense, int64_t B, int32_t M,
+                             const void* unknown_table, const void* yaw, const void* u_att) {
+    if (!params || !sense) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params or sense is NULL");
+    const sc_cbfqp_params* q = &params->qp;
+    if (B < 0 || M < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0 or M < 0");
+    const bool integrator = q->model_id == SC_MODEL_SINGLE_INTEGRATOR2D || q->model_id == SC_MODEL_DOUBLE_INTEGRATOR2D;
+    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && !integrator)
+        return sc::fail(SC_ERR_UNSUPPORTED, "the sensing select / apply are built for DynamicUnicycle2D, SingleIntegrator2D and DoubleIntegrator2D");
+    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (sense->n_unknown < 0 || sense->n_unknown > SC_SENSE_MAX_UNKNOWN)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_unknown outside [0, SC_SENSE_MAX_UNKNOWN]: the sighted rows are one 64-bit mask per agent");
+    if (params->dyn_obs) return sc::fail(SC_ERR_UNSUPPORTED, "the sensing select / apply take static tables: dyn_obs must be 0");
+    if (params->num_constraints < 1 || params->num_constraints > SC_TRACKING_MAX_CONSTRAINTS)
+        return sc::fail(SC_ERR_UNSUPPORTED, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
+    if (sense->att_type != SC_ATT_NONE && sense->att_type != SC_ATT_SIMPLE && sense->att_type != SC_ATT_VELOCITY_TRACKING_YAW)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "att_type must be one of SC_ATT_*");
+    if (sense->att_type != SC_ATT_NONE && !integrator)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "an attitude controller belongs to SingleIntegrator2D / DoubleIntegrator2D: att_type must be SC_ATT_NONE");
+    if (integrator && params->enable_rotation && sense->att_type == SC_ATT_NONE)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "an integrator with enable_rotation = 1 needs an attitude controller (att_type)");
+    if (!std::isfinite(sense->fov_angle) || !(sense->fov_angle > 0) || !std::isfinite(sense->cam_range) || !(sense->cam_range > 0) ||
+        !std::isfinite(sense->w_max) || !(sense->w_max > 0))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "fov_angle, cam_range and w_max must be finite and > 0");
+    if (!(q->dt > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0");
+    if ((size_t)M * 7 * 8 > 150 * 1024) return sc::fail(SC_ERR_UNSUPPORTED, "obstacle table does not fit the LDS");
+    if (sense->n_unknown > 0 && !unknown_table) return sc::fail(SC_ERR_INVALID_ARGUMENT, "unknown_table is NULL with n_unknown > 0");
+    if (integrator && params->enable_rotation && (!yaw || !u_att))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "an integrator with enable_rotation = 1 needs yaw and u_att");
+    return SC_OK;
+}
+
+int sc_tracking_sense_select_batch(const sc_tracking_params* params, const sc_sense_params* sense, int64_t B, int32_t M, const void* X,
+                                   const void* waypoints, const int32_t* n_wp, int32_t* wp_index, int32_t* state_machine, void* goal,
+                                   const void* obs_table, const void* unknown_table, int64_t* seen, const void* yaw, void* u_att,
+                                   const int32_t* ret, void* obs_out, void* goal_out, void* u_ref_out, int32_t* track_out, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    int rc = check_sense_split(params, sense, B, M, unknown_table, yaw, u_att);
+    if (rc != SC_OK) return rc;
+    if (params->max_waypoints < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "max_waypoints < 1");
+    if (!seen) return sc::fail(SC_ERR_INVALID_ARGUMENT, "seen is NULL");
+    if (B > 0 && (!X || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !ret || !obs_out || !goal_out || !u_ref_out ||
+                  !track_out || (M > 0 && !obs_table)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_sense_select_launch(*params, *sense, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal,
+                                                    obs_table, unknown_table, (long long*)seen, yaw, u_att, ret, obs_out, goal_out,
+                                                    u_ref_out, track_out, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "tracking sense select kernel launch");
+    return SC_OK;
+}
+
+int sc_tracking_sense_apply_batch(const sc_tracking_params* params, const sc_sense_params* sense, int64_t B, int32_t M, int32_t step_index,
+                                  void* X, const int32_t* state_machine, const void* goal, const void* obs_table,
+                                  const void* unknown_table, void* yaw, void* u_att, const void* u, const int32_t* u_status, void* u_last,
+                                  int32_t* ret, int32_t* ret_step, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    int rc = check_sense_split(params, sense, B, M, unknown_table, yaw, u_att);
+    if (rc != SC_OK) return rc;
+    if (B > 0 && (!X || !state_machine || !goal || !u || !u_last || !ret || !ret_step || (M > 0 && !obs_table)))
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    if (B == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_sense_apply_launch(*params, *sense, (long long)B, (int)M, (int)step_index, X, state_machine, goal, obs_table,
+                                                   unknown_table, yaw, u_att, u, u_status, u_last, ret, ret_step, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "tracking sense apply kernel launch");
     return SC_OK;
 }
 

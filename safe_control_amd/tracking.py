@@ -7,7 +7,9 @@ checks, robot step and return code all run on the GPU, ``n`` control steps per l
 agent's state resident in registers between steps.  ``BatchedSensingTrackingController`` adds what the
 reference's unknown-environment scenario needs: 'fov' detection of unknown obstacles with their memory,
 and the integrators' heading under the 'simple' / 'velocity_tracking_yaw' attitude controllers
-(csrc/tracking_sense.hip).  Rendering and everything built on polygon geometry stay out of scope: 'ray'
+(csrc/tracking_sense.hip); ``BatchedSensingMPCTrackingController`` flies the same scenario under its default position
+controller 'mpc_cbf', per step sense-select -> one MPC-CBF launch -> sense-apply (csrc/tracking_sense_split.hip).
+Rendering and everything built on polygon geometry stay out of scope: 'ray'
 detection, sensing footprints (return code 1), the 'visibility_*' and 'gatekeeper' attitude controllers.
 
 Host side (this file) only prepares waypoints the way ``set_waypoints`` / ``filter_waypoints`` do
@@ -76,6 +78,10 @@ class BatchedTrackingController:
     nx, nu, ng, npos, wp_cols = 4, 2, 2, 2, 2
     # the per-step entry points of the MPC loop, and what sc_tracking_apply_batch takes between the input and ``u_pos``
     _SPLIT = ("sc_tracking_select_batch", "sc_tracking_apply_batch", (None,))
+    # what the MPC loop records besides traj_X / traj_U (TRAJ_*, one tensor of _split_recorded() each), and whether it keeps the last
+    # selection as ``obs_sel`` / ``u_ref`` / ``track``
+    _SPLIT_MORE = ()
+    _keep_selection = False
     # whether sc_tracking_params carries the speed bounds, the gains of nominal_input and the bicycle's geometry
     _nominal_gains = True
 
@@ -396,6 +402,15 @@ class BatchedTrackingController:
     def _split_params(self):
         return self._tracking_params(1)
 
+    def _split_sensing(self, p):
+        """``(head, select_more, apply_more)`` of this call's select / apply pairs: the parameter structs in front of ``B``, and the
+        pointers select and apply take between the obstacle table and their next argument."""
+        return (C.byref(p),), (), ()
+
+    def _split_recorded(self):
+        """The tensors whose value after a step goes into the buffers of ``_SPLIT_MORE``."""
+        return ()
+
     def _split_solver(self):
         """The MPC object of this call's launches.  Kernel 13 serves superellipsoid rows for the two robots whose DT barrier has that
         branch (csrc/mpc_du_ms_se.hip); other robots' scenes with such rows run on the condensed kernels as before."""
@@ -418,18 +433,22 @@ class BatchedTrackingController:
         goal_c = torch.empty((B, self.ng), dtype=self.tdtype, device=self.device)
         u_ref = torch.empty((B, self.nu), dtype=self.tdtype, device=self.device)
         track = torch.empty(B, dtype=torch.int32, device=self.device)
-        tX, tU = self._record_buffers(n) if record else (None, None)
+        if self._keep_selection:
+            self.obs_sel, self.u_ref, self.track = obs_sel, u_ref, track
+        tX, tU, *tMore = self._record_buffers(n, self._SPLIT_MORE) if record else (None, None)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         obs_ptr = self.obs.data_ptr() if M else None
         select, apply, apply_extra = getattr(self._lib, self._SPLIT[0]), getattr(self._lib, self._SPLIT[1]), self._SPLIT[2]
+        # what a class with more per-agent state hands its entry points: structs behind ``p``, pointers behind the obstacle table
+        head, sel_more, app_more = self._split_sensing(p)
         mpc = self._split_solver()
         i_st, i_it = (2, 3) if self.pos_controller_type == "optimal_decay_mpc_cbf" else (1, 2)     # after u (and the decay multipliers)
         xy_only = self.model == "SingleIntegrator2D"           # csrc/mpc_lin.hip takes its two states
         (xe, ge), u_zero, dummy = self._easy, self._u_zero, self._dummy_obs
         for k in range(n):
             rc = select(
-                C.byref(p), B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(),
-                self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
+                *head, B, M, self.X.data_ptr(), self.waypoints.data_ptr(), self.n_wp.data_ptr(),
+                self.current_goal_index.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr, *sel_more,
                 self.ret.data_ptr(), obs_sel.data_ptr(), goal_c.data_ptr(), u_ref.data_ptr(), track.data_ptr(), stream)
             _lib.check(rc, self._SPLIT[0])
             Xm = self.X[:, :2].contiguous() if xy_only else self.X
@@ -451,14 +470,16 @@ class BatchedTrackingController:
             self.mpc_status = torch.where(track != 0, st, self.mpc_status)
             self.mpc_iters = torch.where(track != 0, its, self.mpc_iters)
             rc = apply(
-                C.byref(p), B, M, self.steps_done + k, self.X.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
-                u.data_ptr(), *apply_extra, self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), stream)
+                *head, B, M, self.steps_done + k, self.X.data_ptr(), self.state_machine.data_ptr(), self.goal.data_ptr(), obs_ptr,
+                *app_more, u.data_ptr(), *apply_extra, self.u_pos.data_ptr(), self.ret.data_ptr(), self.ret_step.data_ptr(), stream)
             _lib.check(rc, self._SPLIT[1])
             if record:
                 tX[k] = self.X
                 tU[k] = self.u_pos
+                for buf, src in zip(tMore, self._split_recorded()):
+                    buf[k] = src
         self.steps_done += n
-        return (self.ret, tX, tU) if record else self.ret
+        return (self.ret, tX, tU, *tMore) if record else self.ret
 
     def run_all_steps(self, tf=30, chunk=200):
         """tracking.py:711-752 for every agent: run int(tf/dt) steps (agents stop at their first -1 / -2)."""
@@ -652,11 +673,15 @@ class BatchedSensingTrackingController(BatchedTrackingController):
     'gatekeeper' attitude controllers.
 
     ``control_step(n, record=False)`` returns ``ret`` or ``(ret, traj_X, traj_U, traj_yaw, traj_seen)``.
+    The position controller is 'cbf_qp'; the scenario's default 'mpc_cbf' is ``BatchedSensingMPCTrackingController``.
     """
 
     MODELS = ("DynamicUnicycle2D", "SingleIntegrator2D", "DoubleIntegrator2D")
     ATT_TYPES = {"simple": _lib.ATT_SIMPLE, "velocity_tracking_yaw": _lib.ATT_VELOCITY_TRACKING_YAW}
     POLYGON_ATT = ("visibility_raycast", "visibility_area", "visibility", "gatekeeper")
+    # the one position controller of the class, and what a caller who asks for another is told
+    POS = "cbf_qp"
+    POS_REFUSAL = "the sensing loop's position controller is 'cbf_qp' here ('mpc_cbf': BatchedSensingMPCTrackingController)"
 
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, unknown_obs=None,
                  io_dtype="f64", device="cuda:0"):
@@ -666,8 +691,8 @@ class BatchedSensingTrackingController(BatchedTrackingController):
         model = robot_spec.get("model")
         if model not in self.MODELS:
             raise ValueError(f"the sensing loop supports {', '.join(self.MODELS)}; not {model!r}")
-        if controller_type.get("pos", "cbf_qp") != "cbf_qp":
-            raise ValueError("the sensing loop's position controller is 'cbf_qp'")
+        if controller_type.get("pos", self.POS) != self.POS:
+            raise ValueError(self.POS_REFUSAL)
         integrator = model != "DynamicUnicycle2D"
         att = controller_type.get("att", "velocity_tracking_yaw")                     # tracking.py:46
         self.att_type = _lib.ATT_NONE
@@ -702,7 +727,7 @@ class BatchedSensingTrackingController(BatchedTrackingController):
                 raise ValueError(f"{name} must be finite and positive")
         unknown_rows = self._normalise_unknown(unknown_obs)
         # the base class refuses a rotating integrator; this class supplies what it lacks, so it is set up as a non-rotating one
-        super().__init__(X0, robot_spec, controller_type={"pos": "cbf_qp"}, dt=dt,
+        super().__init__(X0, robot_spec, controller_type={"pos": self.POS}, dt=dt,
                          enable_rotation=(enable_rotation and not integrator), obs=obs, dyn_obs=False, io_dtype=io_dtype, device=device)
         self.enable_rotation = bool(enable_rotation)
         torch = self.torch
@@ -764,6 +789,49 @@ class BatchedSensingTrackingController(BatchedTrackingController):
         return self._rollout(self._lib.sc_tracking_sense_rollout_batch, (C.byref(p), C.byref(s)), n, record,
                              sensing=(unknown, self.seen.data_ptr(), self.yaw.data_ptr(), self.u_att.data_ptr()),
                              more=TRAJ_YAW_SEEN)
+
+
+class BatchedSensingMPCTrackingController(BatchedSensingTrackingController):
+    """The sensing closed loop under the reference's default position controller of ``examples/test_unknown_env.py``:
+    ``controller_type={'pos': 'mpc_cbf', 'att': ...}`` (``--algo mpc_cbf``; the script's own tuning is horizon 7 and
+    ``mpc_cbf_alpha1 = mpc_cbf_alpha2 = 0.26`` for DynamicUnicycle2D, horizon 9 and 0.32 for DoubleIntegrator2D, :197-206).
+
+    Per control step: sc_tracking_sense_select_batch (goal / state machine, 'fov' detection, memory, nearest-unpassed
+    selection over the known and the remembered unknown rows, nominal input; csrc/tracking_sense_split.hip) -> one MPC-CBF
+    launch for the whole batch -> sc_tracking_sense_apply_batch (attitude controller, collision tests against both tables,
+    robot step, yaw step, return codes).  The solver is the one ``BatchedTrackingController`` picks for the model under
+    'mpc_cbf' (kernel 13 for DynamicUnicycle2D and DoubleIntegrator2D, superellipsoid rows of the known table included,
+    unless ``robot_spec['mpc_formulation'] = 'condensed'``; csrc/mpc_lin.hip for SingleIntegrator2D), with ``mpc_horizon``,
+    ``mpc_cbf_alpha1/2`` and ``num_constraints`` from the spec, and the loop around it is ``_control_step_split``: agents
+    outside 'track' get u_ref, ``u_prev`` / ``mpc_status`` / ``mpc_iters`` as there; MPC failures are not reported.
+
+    Constructor, ``seen``, ``yaw``, ``u_att``, ``set_unknown_obs`` and ``set_waypoints`` as in the parent.  After every
+    step ``obs_sel [B,K,7]``, ``u_ref [B,2]`` and ``track [B]`` hold what each agent's controller was shown.
+    ``control_step(n, record=False)`` returns ``ret`` or ``(ret, traj_X, traj_U, traj_yaw, traj_seen)`` in the parent's layout.
+    """
+
+    POS = "mpc_cbf"
+    POS_REFUSAL = "BatchedSensingMPCTrackingController's position controller is 'mpc_cbf' ('cbf_qp': BatchedSensingTrackingController)"
+    _SPLIT = ("sc_tracking_sense_select_batch", "sc_tracking_sense_apply_batch", (None,))
+    _SPLIT_MORE = TRAJ_YAW_SEEN
+    _keep_selection = True
+
+    def _split_sensing(self, p):
+        s = self._sense_params()
+        self._split_sense_params = s                                # the struct lives as long as the pointer to it
+        unknown = self.unknown_obs.data_ptr() if self.unknown_obs.numel() else None
+        yaw, u_att = self.yaw.data_ptr(), self.u_att.data_ptr()
+        return (C.byref(p), C.byref(s)), (unknown, self.seen.data_ptr(), yaw, u_att), (unknown, yaw, u_att)
+
+    def _split_recorded(self):
+        return self.yaw, self.seen
+
+    def control_step(self, n=1, record=False):
+        """Advance ``n`` control steps, three launches each.  Returns ``ret`` [B], or ``(ret, traj_X [n,B,4], traj_U [n,B,2],
+        traj_yaw [n,B], traj_seen [n,B] int64)`` when ``record``."""
+        if self.waypoints is None:
+            raise RuntimeError("call set_waypoints first")
+        return self._control_step_split(n, record)
 
 
 class BatchedFleetTrackingController(BatchedTrackingController):

@@ -11,7 +11,15 @@ warm-up launch, median (and min .. max) of the repeated runs.
              with 0, 16 and 64 unknown circles: the difference to its own Mu = 0
              row is the detection scan and the two collision scans over the unknown table
 
-Usage: python tools/time_unknown_env.py [steps] [reps]"""
+  mpc        the select / solve / apply loops under 'mpc_cbf' with the tuning of            (4)
+             examples/test_unknown_env.py (:197-206), B = 4096, ms per CONTROL STEP:
+             BatchedTrackingController (sc_tracking_select_batch / _apply_batch around
+             the MPC launch) beside BatchedSensingMPCTrackingController
+             (sc_tracking_sense_select_batch / _apply_batch, csrc/tracking_sense_split.hip)
+             with 0 and 16 unknown circles; the Mu = 0 ratio is what the sensing pair costs
+
+Usage: python tools/time_unknown_env.py [steps] [reps]          legs (1) - (3)
+       python tools/time_unknown_env.py mpc [steps] [reps]      leg (4) alone (20 steps, 3 repetitions by default)"""
 import os
 import statistics
 import sys
@@ -49,7 +57,11 @@ def unknown_rows(Mu, seed=2):
     return np.column_stack([cells % 14 + rng.uniform(0.2, 0.8, Mu), cells // 14 + rng.uniform(0.2, 0.8, Mu), rng.uniform(0.1, 0.2, Mu)])
 
 
-STATE = ("X", "state_machine", "current_goal_index", "goal", "ret", "ret_step", "u_pos", "yaw", "u_att", "seen")
+STATE = ("X", "state_machine", "current_goal_index", "goal", "ret", "ret_step", "u_pos", "yaw", "u_att", "seen",
+         "u_prev", "mpc_status", "mpc_iters")
+# examples/test_unknown_env.py:197-206 (apply_algo_tuning) under --algo mpc_cbf
+MPC_TUNING = {"DynamicUnicycle2D": {"mpc_horizon": 7, "mpc_cbf_alpha1": 0.26, "mpc_cbf_alpha2": 0.26},
+              "DoubleIntegrator2D": {"mpc_horizon": 9, "mpc_cbf_alpha1": 0.32, "mpc_cbf_alpha2": 0.32}}
 
 
 def time_launch(make, steps, reps):
@@ -71,7 +83,37 @@ def time_launch(make, steps, reps):
     return statistics.median(ms), min(ms), max(ms), int((ctl.ret != 0).sum())
 
 
+def mpc_leg(steps, reps, B=4096):
+    """Leg (4): ms per control step of the MPC loops; the plain class is the yardstick (no unknown rows, the same rotation flag)."""
+    obs, wps = scene()
+    mpc = {"pos": "mpc_cbf"}
+    for model, rot in (("DynamicUnicycle2D", True), ("DoubleIntegrator2D", False)):
+        X0 = starts(model, B)
+        spec = dict(SPECS[model], **MPC_TUNING[model])
+
+        def plain():
+            c = sca.BatchedTrackingController(X0, dict(spec), controller_type=mpc, enable_rotation=rot, obs=obs)
+            c.set_waypoints(wps)
+            return c
+
+        p = time_launch(plain, steps, reps)
+        tag = f"{model}{'' if rot else ' (enable_rotation=False)'}"
+        print(f"B={B:6d} {tag:42s} mpc plain     {p[0] / steps:8.3f} ms per control step ({p[1] / steps:.3f} .. {p[2] / steps:.3f}), "
+              f"{p[3]} agents ended in {steps} steps")
+        for Mu in (0, 16):
+            def sense():
+                c = sca.BatchedSensingMPCTrackingController(X0, dict(spec), controller_type=mpc, enable_rotation=rot, obs=obs,
+                                                            unknown_obs=unknown_rows(Mu))
+                c.set_waypoints(wps)
+                return c
+            s = time_launch(sense, steps, reps)
+            print(f"B={B:6d} {tag:42s} mpc sense/{Mu:<2d}  {s[0] / steps:8.3f} ms per control step ({s[1] / steps:.3f} .. {s[2] / steps:.3f})  "
+                  f"x{s[0] / p[0]:.3f} of plain, {s[3]} agents ended")
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "mpc":
+        return mpc_leg(int(sys.argv[2]) if len(sys.argv) > 2 else 20, int(sys.argv[3]) if len(sys.argv) > 3 else 3)
     steps = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     obs, wps = scene()
