@@ -156,10 +156,19 @@ def make_slices(caps=(), order=True, classify_first=False):
     return sl
 
 
+def grown_workspace(ws, need, device, floor=0):
+    """The byte tensor a batched class keeps between calls as a kernel's workspace: ``ws`` where it holds ``need`` bytes on
+    ``device``, else a new one of ``max(need, floor)``."""
+    if ws is None or ws.numel() < need or ws.device != device:
+        import torch
+        ws = torch.empty((max(need, floor),), dtype=torch.uint8, device=device)
+    return ws
+
+
 class SlicedSolver:
     """What the batched MPC classes share for their continuation launches: the schedule (``iter_slices``: iteration caps of the
     launches before the last one; ``classify_first``; ``order``) and a workspace tensor that is kept between calls and grows with
-    the batch.  ``slices_for(B, need_bytes, device)`` returns the ctypes struct to pass, or None for a single launch."""
+    the batch.  ``slices_for(need_bytes_fn, device)`` returns the ctypes struct to pass, or None for a single launch."""
 
     def init_slices(self, iter_slices=None, classify_first=True, order=True):
         """iter_slices: None = the default schedule (FIRST_CAP), () = one launch"""
@@ -168,14 +177,11 @@ class SlicedSolver:
         self._slice_ws = None
 
     def slices_for(self, need_bytes_fn, device):
-        import torch
         caps = [c for c in self.iter_slices if c < self.max_iter]
         if not caps and not self.classify_first:
             return None
         sl = make_slices(caps, self.order_slices, self.classify_first)
-        need = int(need_bytes_fn())
-        if self._slice_ws is None or self._slice_ws.numel() < need or self._slice_ws.device != device:
-            self._slice_ws = torch.empty((need,), dtype=torch.uint8, device=device)
+        self._slice_ws = grown_workspace(self._slice_ws, int(need_bytes_fn()), device)
         sl.workspace, sl.workspace_bytes = self._slice_ws.data_ptr(), self._slice_ws.numel()
         return sl
 

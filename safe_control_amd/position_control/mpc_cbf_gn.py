@@ -4,13 +4,11 @@
 model from the one MPCCBF class, position_control/mpc_cbf.py:7-100); ``BatchedGnMPCCBF`` solves B agents per launch on
 device tensors.  No CPU fallback.
 """
-import ctypes as C
-
 import numpy as np
 
 from .. import _lib
-from ..robots.spec import complete_robot_spec
-from .mpc_cbf import apply_mpc_overrides, pad_obstacles
+from ._mpc_host import BatchedCondensedMpc, MpcDropIn
+from .mpc_cbf import apply_mpc_overrides
 
 GN_MODELS = ("DoubleIntegrator2D", "Quad2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF")
 
@@ -70,34 +68,21 @@ def make_params(robot_spec, mc, cbf_param, horizon, dt, radius, io_dtype, obs_sh
     return p
 
 
-class GnMPCCBF:
+class GnMPCCBF(MpcDropIn):
     """Drop-in for position_control.mpc_cbf.MPCCBF with a DoubleIntegrator2D, Quad2D or KinematicBicycle2D robot."""
 
-    def __init__(self, robot, robot_spec, show_mpc_traj=False, num_obs=5, device=0):
-        self.robot = robot
-        self.robot_spec = complete_robot_spec(robot_spec)
-        self.status = "optimal"                               # mpc_cbf.py:10
-        self.show_mpc_traj = show_mpc_traj
-        self.num_obs = int(num_obs)
-        self.device = device
+    def _model(self):
         self.horizon = int(self.robot_spec.get("mpc_horizon", 10))
-        self.dt = robot.dt
         self._mc = model_constants(self.robot_spec)
         self.Q, self.R = np.diag(self._mc["Q"]), np.array(self._mc["R"])
         self.n_states, self.n_controls = self._mc["nx"], 2
-        self.goal = np.array([0, 0])
         self.cbf_param = apply_mpc_overrides(dict(self._mc["cbf_param"]), self.robot_spec)
-        self.obs = None
-        self.setup_control_problem()
 
     def setup_control_problem(self):
         if not 1 <= self.horizon <= 32:
             raise ValueError("mpc_horizon must be in [1, 32]")
         self._lib = _lib.load()
-        self.u_prev = np.zeros(2)
-        self.z = np.zeros(2 * self.horizon)
-        self.iterations = 0
-        self.solver_status = "optimal"
+        self._init_state()
         # DoubleIntegrator2D: the NLP as do-mpc poses it (multiple shooting under IPOPT's algorithm, csrc/mpc_du_ms.hip, kernel 13) unless
         # robot_spec['mpc_formulation'] = 'condensed'; superellipsoid rows run on the condensed kernel.  KinematicBicycle2D: the same kernel ON
         # REQUEST (robot_spec['mpc_formulation'] = 'multiple_shooting'): where a plan slows down to v_min the kink of robot.step's speed clip sits
@@ -109,96 +94,32 @@ class GnMPCCBF:
             from .mpc_cbf_ms import BatchedMSMPCCBF
             self._ms = BatchedMSMPCCBF(self.robot_spec, dt=self.dt, io_dtype="f64", horizon=self.horizon, cbf_param=self.cbf_param, check_circles=False)
 
-    def update_tvp(self, goal, obs):
-        self.goal = np.array(goal)
-        self.obs = pad_obstacles(obs, self.num_obs)
-
-    def solve_control_problem(self, robot_state, control_ref, nearest_obs):
-        self.update_tvp(control_ref["goal"], nearest_obs)
-        if control_ref["state_machine"] != "track":           # mpc_cbf.py:379-381
-            return control_ref["u_ref"]
-        nx = self._mc["nx"]
-        X = np.zeros(nx)
-        xs = np.asarray(robot_state, dtype=np.float64).reshape(-1)[:nx]
-        X[: xs.shape[0]] = xs
-        g = np.ascontiguousarray(np.asarray(self.goal, dtype=np.float64).reshape(-1)[:2])
-        obs = np.ascontiguousarray(self.obs, dtype=np.float64)
+    def _solve_track(self, X, g, obs):
         se = bool((obs[:, 6] >= 0.5).any())
         if self._ms is not None and (not se or self.robot_spec["model"] == "DoubleIntegrator2D"):      # (superellipsoid rows: csrc/mpc_du_ms_se.hip)
-            import torch
             self._ms.superellipsoids = se
-            dev = torch.device("cuda", int(self.device))
-            t = lambda a: torch.tensor(np.ascontiguousarray(a, dtype=np.float64), dtype=torch.float64, device=dev)     # noqa: E731
-            self._ms.cbf_param = self.cbf_param
-            self._ms.robot_spec["radius"] = self.robot.robot_radius
-            u, st, it, plan = self._ms.solve(t(X[None]), t(self.u_prev[None]), t(g[None]), t(obs[None]), want_plan=True)
-            self.iterations = int(it[0].item())
-            self.solver_status = _lib.STATUS_STRINGS[int(st[0].item())]
-            self.z = plan[0, (self.horizon + 1) * 4:].cpu().numpy().copy()
-            self.u_prev = u[0].cpu().numpy().copy()
-            return self.u_prev.reshape(-1, 1).copy()
+            return self._solve_batched(self._ms, X, g, obs, want_plan=True)
         p = make_params(self.robot_spec, self._mc, self.cbf_param, self.horizon, self.dt, self.robot.robot_radius, _lib.DTYPE_F64)
-        u = np.zeros(2); st = np.zeros(1, dtype=np.int32); it = np.zeros(1, dtype=np.int32)
-        rc = self._lib.sc_mpcgn_solve_batch_host(
-            C.byref(p), 1, self.num_obs, X.ctypes.data, self.u_prev.ctypes.data, g.ctypes.data, obs.ctypes.data,
-            u.ctypes.data, st.ctypes.data, it.ctypes.data, self.z.ctypes.data, int(self.device))
-        _lib.check(rc, "sc_mpcgn_solve_batch_host")
-        self.iterations = int(it[0])
-        self.solver_status = _lib.STATUS_STRINGS[int(st[0])]
-        self.u_prev = u.copy()
-        return u.reshape(-1, 1).copy()
+        return self._solve_host("sc_mpcgn_solve_batch_host", p, X, g, obs)
 
 
-class BatchedGnMPCCBF(_lib.SlicedSolver):
+class BatchedGnMPCCBF(BatchedCondensedMpc):
     """``solve(X[B,nx], u_prev[B,2], goal[B,2], obs[B,K,7] | obs[K,7])`` -> ``u[B,2]``, ``status[B]``, ``iters[B]`` (and
-    ``z[B,2N]`` if asked); nx = 4 (DoubleIntegrator2D, KinematicBicycle2D) or 6 (Quad2D)."""
+    ``z[B,2N]`` if asked); nx = 4 (DoubleIntegrator2D, KinematicBicycle2D) or 6 (Quad2D).  ``resto``: a _lib.RestoParams override."""
+    stem = "sc_mpcgn"
 
     def __init__(self, robot_spec, dt=0.05, io_dtype="f64", horizon=None, cbf_param=None, tol=1e-6, max_iter=_lib.IPOPT_MAX_ITER,
                  iter_slices=None, classify_first=True, order=True):
-        self.init_slices(iter_slices, classify_first, order)      # continuation launches (include/safe_control_amd.h: sc_mpc_slices)
-        self.robot_spec = complete_robot_spec(robot_spec)
+        self.resto = None
+        super().__init__(robot_spec, dt, io_dtype, horizon, cbf_param, tol, max_iter, iter_slices, classify_first, order)
+
+    def _model(self):
         if self.robot_spec["model"] not in GN_MODELS:
             raise NotImplementedError(f"this controller serves {GN_MODELS}")
-        self.dt = float(dt)
-        self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]
-        self.horizon = int(horizon if horizon is not None else self.robot_spec.get("mpc_horizon", 10))
         self._mc = model_constants(self.robot_spec)
-        self.Q, self.R = np.diag(self._mc["Q"]), np.array(self._mc["R"])
-        self.cbf_param = cbf_param or apply_mpc_overrides(dict(self._mc["cbf_param"]), self.robot_spec)
-        self.tol, self.max_iter = tol, max_iter
-        self._lib = _lib.load()
+        self.Q, self.R, self.nx = np.diag(self._mc["Q"]), np.array(self._mc["R"]), self._mc["nx"]
+        return apply_mpc_overrides(dict(self._mc["cbf_param"]), self.robot_spec)
 
-    @property
-    def torch_dtype(self):
-        import torch
-        return torch.float32 if self.io_dtype == _lib.DTYPE_F32 else torch.float64
-
-    def solve(self, X, u_prev, goal, obs, want_z=False):
-        import torch
-        dt_ = self.torch_dtype
-        for name, t in (("X", X), ("u_prev", u_prev), ("goal", goal), ("obs", obs)):
-            if not (t.is_cuda and t.is_contiguous() and t.dtype == dt_):
-                raise ValueError(f"{name} must be a contiguous CUDA tensor of dtype {dt_}")
-        B = X.shape[0]
-        nx = self._mc["nx"]
-        shared = obs.dim() == 2
-        K = obs.shape[-2]
-        if X.shape != (B, nx) or u_prev.shape != (B, 2) or goal.shape != (B, 2) or obs.shape[-1] != 7 \
-                or (not shared and obs.shape[0] != B):
-            raise ValueError(f"expected X[B,{nx}], u_prev[B,2], goal[B,2], obs[B,K,7] or obs[K,7]")
-        u = torch.empty((B, 2), dtype=dt_, device=X.device)
-        status = torch.empty((B,), dtype=torch.int32, device=X.device)
-        iters = torch.empty((B,), dtype=torch.int32, device=X.device)
-        z = torch.empty((B, 2 * self.horizon), dtype=dt_, device=X.device) if want_z else None
-        p = make_params(self.robot_spec, self._mc, self.cbf_param, self.horizon, self.dt, self.robot_spec["radius"],
-                        self.io_dtype, obs_shared=shared, tol=self.tol, max_iter=self.max_iter, resto=getattr(self, "resto", None))
-        stream = torch.cuda.current_stream(X.device).cuda_stream
-        sl = self.slices_for(lambda: self._lib.sc_mpcgn_slices_workspace_bytes(C.byref(p), B, K), X.device)
-        args = (B, K, X.data_ptr(), u_prev.data_ptr(), goal.data_ptr(), obs.data_ptr(), u.data_ptr(),
-                status.data_ptr(), iters.data_ptr(), z.data_ptr() if z is not None else None, stream)
-        if sl is None:
-            rc = self._lib.sc_mpcgn_solve_batch(C.byref(p), *args)
-        else:
-            rc = self._lib.sc_mpcgn_solve_batch_sliced(C.byref(p), C.byref(sl), *args)
-        _lib.check(rc, "sc_mpcgn_solve_batch")
-        return (u, status, iters, z) if want_z else (u, status, iters)
+    def _params(self, obs_shared=False):
+        return make_params(self.robot_spec, self._mc, self.cbf_param, self.horizon, self.dt, self.robot_spec["radius"],
+                           self.io_dtype, obs_shared=obs_shared, tol=self.tol, max_iter=self.max_iter, resto=self.resto)

@@ -127,6 +127,23 @@ def test_drop_in_class_and_bad_arguments():
         ctl.solve(t(np.zeros((2, 4))), t(np.zeros((2, 2))), t(np.zeros((2, 2))), t(np.zeros((2, 1, 7))))
 
 
+def test_drop_in_double_integrator_on_this_kernel():
+    """robot_spec['mpc_formulation'] = 'condensed': the DoubleIntegrator2D drop-in on this kernel's host-pointer entry point (its default is
+    kernel 13, which the loop above runs).  Two agents, one obstacle, horizon 5."""
+    mdl = G.di_model()
+    rng = np.random.default_rng(5)
+    for _ in range(2):
+        x0, goal, obs = draw(mdl, rng, 1)
+        robot = sca.RobotHandle(x0, {"model": "DoubleIntegrator2D"})
+        ctl = sca.MPCCBF(robot, dict(robot.robot_spec, mpc_formulation="condensed", mpc_horizon=5), num_obs=1)
+        assert type(ctl).__name__ == "GnMPCCBF" and ctl._ms is None and ctl.horizon == 5
+        u = ctl.solve_control_problem(robot.X, {"state_machine": "track", "u_ref": np.zeros((2, 1)), "goal": goal}, obs)
+        uo, so, _, info = G.solve(mdl, x0, np.zeros(2), goal, obs, N=5, return_info=True)
+        assert ctl.solver_status == sca._lib.STATUS_STRINGS[so]
+        if so == 0:
+            assert u.shape == (2, 1) and np.abs(u.reshape(-1) - uo).max() <= (1e-6 if info["err"] <= 1e-6 else 1e-4) * max(1.0, np.abs(uo).max())
+
+
 def test_non_finite_inputs_terminate_and_are_not_reported_optimal():
     for name in MODELS:
         mdl = MODELS[name]()
