@@ -7,12 +7,12 @@ trajectory and ``solve_control_problem(state, friction=...)``.  Anything else ra
 ``BatchedDriftShield`` runs B cars per launch on device tensors, and the example's closed loop (with a lane keeper as the
 nominal planner) fused in one launch.  No CPU fallback.
 """
-import ctypes as C
 import math
 
 import numpy as np
 
 from .. import _lib
+from ._shield_host import BatchedShieldBase, MpsDropIn, ShieldDropIn
 
 DRIFT_MODELS = ("DynamicBicycle2D", "DriftingCar")
 
@@ -75,14 +75,7 @@ def _fill_controller(dst, c):
         setattr(dst, k, float(c.get(k, 0.0)))
 
 
-def _algo_id(algo):
-    ids = {"gatekeeper": _lib.SHIELD_GATEKEEPER, "mps": _lib.SHIELD_MPS}
-    if algo not in ids:
-        raise ValueError(f"algo must be one of {sorted(ids)}")
-    return ids[algo]
-
-
-class BatchedDriftShield:
+class BatchedDriftShield(BatchedShieldBase):
     """B drifting cars per launch, each with its own Gatekeeper or MPS state on the device.
 
     ``backup`` is "lane_change" (to lane ``backup_lane`` of ``track``), "stop", or a dict of controller numbers
@@ -92,6 +85,7 @@ class BatchedDriftShield:
     u[B, C+n_backup, 2]``); obstacle tables are ``[B, n, 3]`` (x, y, radius) and ``[B, n, 7]`` (x, y, vx, vy, length, width,
     radius), or one ``[n, .]`` table for all cars; without nominal inputs a lane keeper aimed at lane ``ego_lane`` plans on the
     device.  ``rollout(...)`` runs the example's closed loop.  ``fields(state, B)`` decodes the state buffer."""
+    nx, extra, stem, what = 8, ("commit_friction",), "sc_drift_shield", "drift shield"
 
     def __init__(self, algo="gatekeeper", backup="lane_change", robot_spec=None, track=None, dt=0.05, backup_horizon=3.0, nominal_horizon=6.0,
                  event_offset=0.05, safety_margin=0.01, horizon_discount=None, io_dtype="f64", max_nominal=None, ego_lane=1, backup_lane=3,
@@ -103,30 +97,16 @@ class BatchedDriftShield:
         self.track = dict(default_track(), **(track or {}))
         if self.track.get("track_type", "straight") != "straight":
             raise NotImplementedError("the native drift shields serve the straight track only (not 'oval' / 'l_shape')")
-        self.algo, self.robot_spec = _algo_id(algo), spec
+        super().__init__(algo, spec, dt, backup_horizon, nominal_horizon, event_offset, safety_margin, horizon_discount, io_dtype, max_nominal)
         if isinstance(backup, str):
             if backup not in ("lane_change", "stop"):
                 raise NotImplementedError("backup must be 'lane_change', 'stop' or a dict of controller numbers")
             backup = stopping_controller(spec) if backup == "stop" else lane_change_controller(spec, lane_center(self.track, backup_lane))
         self.backup = dict(backup)
         self.keeper = lane_change_controller(spec, lane_center(self.track, ego_lane))
-        self.dt, self.event_offset, self.safety_margin = float(dt), float(event_offset), float(safety_margin)
-        self.n_backup = int(backup_horizon / dt)                                       # gatekeeper.py:323
-        hd = horizon_discount if horizon_discount is not None else 5 * dt                # :67
-        self.discount_steps = max(1, int(hd / dt))                                        # :600
-        self.n_nominal = int(nominal_horizon / dt)
-        self.max_nominal = int(max_nominal) if max_nominal is not None else max(1, self.n_nominal)
-        self.io_dtype = _lib.DTYPE_F32 if io_dtype in ("f32", "float32") else _lib.DTYPE_F64
         self.puddles = [tuple(float(v) for v in p) for p in puddles]
         if len(self.puddles) > _lib.DRIFT_MAX_PUDDLES:
             raise NotImplementedError(f"more than {_lib.DRIFT_MAX_PUDDLES} puddles")
-        import torch  # noqa: F401  (torch's HIP runtime has to be the process's first: loaded after the library's, it sees no device)
-        self._lib = _lib.load()
-
-    @property
-    def torch_dtype(self):
-        import torch
-        return torch.float32 if self.io_dtype == _lib.DTYPE_F32 else torch.float64
 
     def params(self, n_nominal=None, n_static=0, n_moving=0, obs_shared=False):
         p = _lib.DriftShieldParams()
@@ -147,37 +127,12 @@ class BatchedDriftShield:
         _fill_controller(p.keeper, self.keeper)
         return p
 
-    def state_bytes(self, B):
-        n = int(self._lib.sc_drift_shield_state_bytes(C.byref(self.params()), int(B)))
-        if n == 0 and B > 0:
-            raise ValueError("invalid drift shield parameters")
-        return n
-
-    def new_state(self, B, device="cuda"):
-        import torch
-        return torch.zeros((self.state_bytes(B),), dtype=torch.uint8, device=device)
-
-    def fields(self, state, B):
-        """Views of the state buffer: s, idx, clen, init (int32 [B]), net, commit_friction (float64 [B]), cursor (float64 [B,8])."""
-        import torch
-        o_cur = B * self.max_nominal * 16
-        o_cmu = o_cur + B * 64
-        o_net = o_cmu + B * 8
-        o_int = o_net + B * 8
-        ints = state[o_int:o_int + 16 * B].view(torch.int32).view(4, B)
-        return dict(s=ints[0], idx=ints[1], clen=ints[2], init=ints[3], net=state[o_net:o_int].view(torch.float64),
-                    commit_friction=state[o_cmu:o_net].view(torch.float64), cursor=state[o_cur:o_cmu].view(torch.float64).view(B, 8))
-
     def _check(self, X, friction, state, static_obs, moving_obs, *rest):
-        dt_ = self.torch_dtype
-        for name, t in (("X", X), ("friction", friction), ("static_obs", static_obs), ("moving_obs", moving_obs)) + tuple(rest):
-            if t is not None and not (t.is_cuda and t.is_contiguous() and t.dtype == dt_):
-                raise ValueError(f"{name} must be a contiguous CUDA tensor of dtype {dt_}")
+        self._check_tensors((("X", X), ("friction", friction), ("static_obs", static_obs), ("moving_obs", moving_obs)) + tuple(rest))
         B = X.shape[0]
         if X.shape != (B, 8) or friction.shape != (B,):
             raise ValueError("expected X[B,8], friction[B]")
-        if not (state.is_cuda and state.is_contiguous() and state.numel() == self.state_bytes(B)):
-            raise ValueError("state must be a contiguous CUDA buffer of state_bytes(B) bytes (new_state(B))")
+        self._check_state(state, B)
         counts, shared = [], []
         for name, t, w in (("static_obs", static_obs, 3), ("moving_obs", moving_obs, 7)):
             if t is None or t.numel() == 0:
@@ -194,76 +149,27 @@ class BatchedDriftShield:
         return B, counts[0], counts[1], bool(shared and shared[0])
 
     def step(self, X, friction, state, nominal_x=None, nominal_u=None, static_obs=None, moving_obs=None, want_committed=False):
-        import torch
         B, ns, nm, shared = self._check(X, friction, state, static_obs, moving_obs, ("nominal_x", nominal_x), ("nominal_u", nominal_u))
-        M = self.n_nominal
-        if nominal_x is not None:
-            M = nominal_x.shape[1] - 1
-            if nominal_x.shape != (B, M + 1, 8) or nominal_u is None or nominal_u.shape != (B, M, 2):
-                raise ValueError("expected nominal_x[B, M+1, 8] and nominal_u[B, M, 2]")
-        dev = X.device
-        u = torch.empty((B, 2), dtype=self.torch_dtype, device=dev)
-        using = torch.empty((B,), dtype=torch.int32, device=dev)
-        s = torch.empty((B,), dtype=torch.int32, device=dev)
-        cx = cu = None
-        if want_committed:
-            cx = torch.full((B, self.max_nominal + 1 + self.n_backup, 8), float("nan"), dtype=self.torch_dtype, device=dev)
-            cu = torch.full((B, self.max_nominal + self.n_backup, 2), float("nan"), dtype=self.torch_dtype, device=dev)
-        p = self.params(M, ns, nm, shared)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        rc = self._lib.sc_drift_shield_step_batch(C.byref(p), B, X.data_ptr(), friction.data_ptr(), ptr(static_obs), ptr(moving_obs),
-                                                  ptr(nominal_x), ptr(nominal_u), state.data_ptr(), u.data_ptr(), using.data_ptr(),
-                                                  s.data_ptr(), ptr(cx), ptr(cu), stream)
-        _lib.check(rc, "sc_drift_shield_step_batch")
-        return (u, using, s, cx, cu) if want_committed else (u, using, s)
+        return self._run_step(X, (friction, static_obs, moving_obs), state, nominal_x, nominal_u, want_committed,
+                              n_static=ns, n_moving=nm, obs_shared=shared)
 
     def rollout(self, X, friction, moving_obs, state, ret, ret_step, n_ctrl, step_offset=0, backup_steps=None, static_obs=None):
         """n_ctrl steps of the example's loop in one launch; X, friction, moving_obs ([B, n, 7]), state, ret, ret_step (and
         backup_steps) are updated in place.  Returns (u, using_backup) of the last step."""
-        import torch
         B, ns, nm, shared = self._check(X, friction, state, static_obs, moving_obs)
         if shared:
             raise ValueError("rollout moves the obstacles: it needs one table per car ([B, n, .])")
-        dev = X.device
-        u = torch.empty((B, 2), dtype=self.torch_dtype, device=dev)
-        using = torch.empty((B,), dtype=torch.int32, device=dev)
-        p = self.params(None, ns, nm, False)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-        rc = self._lib.sc_drift_shield_rollout_batch(C.byref(p), B, int(n_ctrl), int(step_offset), X.data_ptr(), friction.data_ptr(),
-                                                     ptr(static_obs), ptr(moving_obs), state.data_ptr(), u.data_ptr(), using.data_ptr(),
-                                                     ret.data_ptr(), ret_step.data_ptr(), ptr(backup_steps), stream)
-        _lib.check(rc, "sc_drift_shield_rollout_batch")
-        return u, using
+        return self._run_rollout(self.params(None, ns, nm, False), X, (friction, static_obs, moving_obs), state, ret, ret_step, n_ctrl,
+                                 step_offset, backup_steps)
 
 
-class Gatekeeper:
+class Gatekeeper(ShieldDropIn):
     """Drop-in for shielding.gatekeeper.Gatekeeper on the drift-car scenario (one car per call)."""
+    n_states, _served, _ctrl = 8, "the native drift shields", None
 
-    _algo = "gatekeeper"
-
-    def __init__(self, robot, robot_spec, dt=0.05, backup_horizon=2.0, event_offset=0.5, ax=None, nominal_horizon=None,
-                 horizon_discount=None, safety_margin=1.0, device=0):
+    def _refuse_model(self, robot_spec):
         if robot_spec.get("model", "DynamicBicycle2D") not in DRIFT_MODELS:
             raise NotImplementedError("the native drift shields serve the DriftingCar on DynamicBicycle2D")
-        self.robot, self.robot_spec, self.dt = robot, robot_spec, dt
-        self.backup_horizon, self.event_offset, self.safety_margin = backup_horizon, event_offset, safety_margin
-        self.horizon_discount = horizon_discount if horizon_discount is not None else 5 * dt
-        self.nominal_horizon = nominal_horizon if nominal_horizon is not None else backup_horizon
-        self.n_states, self.n_controls = 8, 2
-        self.nominal_controller = self.backup_controller = self.backup_target = None
-        self.env = self.moving_obstacles = None
-        self.nominal_x_traj = self.nominal_u_traj = None
-        self.next_event_time, self.current_time_idx, self.committed_horizon, self.actual_nominal_steps = 0.0, int(backup_horizon / dt), 0.0, 0
-        self.committed_x_traj = self.committed_u_traj = None
-        self._device = device
-        self._batched = self._state = self._cx = self._cu = self._ctrl = None
-        self._cap = self._clen = 0
-        self._using_backup = True
-
-    def set_nominal_controller(self, nominal_controller):
-        self.nominal_controller = nominal_controller
 
     def set_backup_controller(self, backup_controller, target=None):
         self._ctrl = controller_from_object(backup_controller, target)
@@ -277,18 +183,6 @@ class Gatekeeper:
             raise NotImplementedError(f"more than {_lib.DRIFT_MAX_OBS} static obstacles")
         self.env = env
         self._batched = self._state = None
-
-    def set_nominal_trajectory(self, nominal_x_traj, nominal_u_traj):
-        # the reference's transposition rule (gatekeeper.py:188-205)
-        for name, tr in (("nominal_x_traj", nominal_x_traj), ("nominal_u_traj", nominal_u_traj)):
-            if tr is not None:
-                tr = np.asarray(tr)
-                if tr.ndim == 2 and tr.shape[0] < tr.shape[1]:
-                    tr = tr.T
-                setattr(self, name, np.array(tr))
-
-    def set_moving_obstacles(self, obstacles):
-        self.moving_obstacles = obstacles
 
     def _moving_table(self):
         """[n, 7] rows from the predictor at t = 0 (get_dynamic_obstacle_states): constant velocity, rectangle, radius."""
@@ -324,88 +218,21 @@ class Gatekeeper:
     def _static_table(self):
         return np.array([[o["x"], o["y"], o["spec"].get("radius", 2.5)] for o in getattr(self.env, "obstacles", ())], dtype=np.float64).reshape(-1, 3)
 
-    def _setup(self, M):
-        if self.env is None or self.backup_controller is None:
-            raise RuntimeError("set_environment() and set_backup_controller() first")
-        if self._batched is not None and M > self._cap:
-            raise NotImplementedError("the nominal trajectory grew beyond the length of the first call: create a new shield")
-        if self._batched is None:
-            self._cap = max(M, 1)
-            if self._cap > _lib.DRIFT_MAX_NOMINAL:
-                raise NotImplementedError(f"nominal trajectories longer than {_lib.DRIFT_MAX_NOMINAL} steps")
-            track = dict(track_type="straight", track_length=float(self.env.track_length), track_width=float(self.env.track_width),
-                         num_lanes=int(getattr(self.env, "num_lanes", 1)))
-            self._batched = BatchedDriftShield(self._algo, self._ctrl, dict(self.robot_spec), track, self.dt, self.backup_horizon,
-                                               nominal_horizon=M * self.dt, event_offset=self.event_offset, safety_margin=self.safety_margin,
-                                               horizon_discount=self.horizon_discount, max_nominal=self._cap)
-            self._state = self._batched.new_state(1, device=f"cuda:{self._device}")
+    def _make_batched(self, M):
+        if self._cap > _lib.DRIFT_MAX_NOMINAL:
+            raise NotImplementedError(f"nominal trajectories longer than {_lib.DRIFT_MAX_NOMINAL} steps")
+        track = dict(track_type="straight", track_length=float(self.env.track_length), track_width=float(self.env.track_width),
+                     num_lanes=int(getattr(self.env, "num_lanes", 1)))
+        return BatchedDriftShield(self._algo, self._ctrl, dict(self.robot_spec), track, self.dt, self.backup_horizon,
+                                  nominal_horizon=M * self.dt, event_offset=self.event_offset, safety_margin=self.safety_margin,
+                                  horizon_discount=self.horizon_discount, max_nominal=self._cap)
 
-    def solve_control_problem(self, robot_state, friction=None):
-        import torch
-        if self.nominal_controller is not None:
-            raise NotImplementedError("forward-propagation mode (set_nominal_controller) is not served: pass set_nominal_trajectory")
-        if self.nominal_x_traj is None or self.nominal_u_traj is None:
-            raise NotImplementedError("the native drift shields need the external nominal trajectory (set_nominal_trajectory)")
-        nx = np.asarray(self.nominal_x_traj, dtype=np.float64).reshape(-1, 8)
-        M = len(nx) - 1
-        nu = np.asarray(self.nominal_u_traj, dtype=np.float64).reshape(-1, 2)[:M]
-        if len(nu) < M:
-            raise ValueError("nominal_u_traj is shorter than nominal_x_traj - 1")
-        self._setup(M)
+    def _call_inputs(self, t, friction):
         if friction is None:                                      # the reference rolls out with the robot's current friction
             friction = self.robot.get_friction() if hasattr(self.robot, "get_friction") else self.robot_spec.get("mu", 1.0)
-        x = np.asarray(robot_state, dtype=np.float64).flatten()
-        dev = torch.device("cuda", self._device)
-        t = lambda a: torch.tensor(np.ascontiguousarray(a), dtype=torch.float64, device=dev)
-        cap_x = self._cap + 1 + self._batched.n_backup
-        if self._cx is None or self._cx.shape[1] != cap_x:
-            self._cx = torch.full((1, cap_x, 8), float("nan"), dtype=torch.float64, device=dev)
-            self._cu = torch.full((1, cap_x - 1, 2), float("nan"), dtype=torch.float64, device=dev)
         sob, mob = self._static_table(), self._moving_table()
-        p = self._batched.params(M, len(sob), len(mob), False)
-        u = torch.empty((1, 2), dtype=torch.float64, device=dev)
-        using = torch.empty((1,), dtype=torch.int32, device=dev)
-        Xt, ft, nxt, nut, st, mt = t(x.reshape(1, 8)), t([float(friction)]), t(nx[None]), t(nu[None]), t(sob[None]), t(mob[None])
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        rc = self._batched._lib.sc_drift_shield_step_batch(C.byref(p), 1, Xt.data_ptr(), ft.data_ptr(), st.data_ptr() if len(sob) else None,
-                                                           mt.data_ptr() if len(mob) else None, nxt.data_ptr(), nut.data_ptr(),
-                                                           self._state.data_ptr(), u.data_ptr(), using.data_ptr(), None,
-                                                           self._cx.data_ptr(), self._cu.data_ptr(), stream)
-        _lib.check(rc, "sc_drift_shield_step_batch")
-        f = self._batched.fields(self._state, 1)
-        self._using_backup = bool(using.item())
-        self.actual_nominal_steps = int(f["s"].item())
-        self.current_time_idx = int(f["idx"].item())
-        self.next_event_time = float(f["net"].item())
-        self._clen = int(f["clen"].item())
-        self.committed_horizon = self.actual_nominal_steps * self.dt
-        self.committed_x_traj = self.committed_u_traj = None
-        return u.cpu().numpy().reshape(-1, 1)
-
-    def get_committed_trajectory(self):
-        if self._state is None:
-            return None, None
-        if self.committed_x_traj is None:
-            n = self._clen
-            self.committed_x_traj, self.committed_u_traj = self._cx[0, :n + 1].cpu().numpy(), self._cu[0, :n].cpu().numpy()
-        return self.committed_x_traj, self.committed_u_traj
-
-    def get_committed_horizon(self):
-        return self.committed_horizon
-
-    def is_using_backup(self):
-        return self._using_backup
-
-    def get_status(self):
-        return {"current_time_idx": self.current_time_idx, "committed_horizon": self.committed_horizon,
-                "next_event_time": self.next_event_time, "using_backup": self.is_using_backup(),
-                "committed_length": self._clen if self._state is not None else 0}
+        return (t([float(friction)]), t(sob[None]), t(mob[None])), dict(n_static=len(sob), n_moving=len(mob))
 
 
-class MPS(Gatekeeper):
+class MPS(MpsDropIn, Gatekeeper):
     """Drop-in for shielding.mps.MPS on the drift-car scenario: one nominal step, re-evaluated at every call."""
-
-    _algo = "mps"
-
-    def __init__(self, robot, robot_spec, dt=0.05, backup_horizon=2.0, event_offset=0.5, ax=None, safety_margin=1.0, device=0):
-        super().__init__(robot, robot_spec, dt, backup_horizon, event_offset, ax, safety_margin=safety_margin, device=device)

@@ -3,13 +3,9 @@
 ``MPS`` keeps the surface of the reference class (shielding/mps.py): the Gatekeeper drop-in's with the MPS constructor
 (no nominal horizon, no discount), one candidate with one nominal step per call, and is_using_backup() = the output
 differs from nominal_u_traj[0] by 1e-2 or more (mps.py:145-157)."""
+from ._shield_host import MpsDropIn
 from .gatekeeper import Gatekeeper
 
 
-class MPS(Gatekeeper):
+class MPS(MpsDropIn, Gatekeeper):
     """Drop-in for shielding.mps.MPS on the evade scenario (one robot per call)."""
-
-    _algo = "mps"
-
-    def __init__(self, robot, robot_spec, dt=0.05, backup_horizon=2.0, event_offset=0.5, ax=None, safety_margin=1.0, device=0):
-        super().__init__(robot, robot_spec, dt, backup_horizon, event_offset, ax, safety_margin=safety_margin, device=device)
