@@ -120,6 +120,7 @@ int         sc_device_count(int* count_out);  /* number of visible HIP devices  
  * status_out [B] int32: SC_STATUS_*.
  * h_out [B,K] or NULL: barrier value h(x) per obstacle row (0 for rows >= n_obs[i]).
  * Element type of X/u_ref/obs/u_out/h_out is params->io_dtype.
+ * robot_radius, alpha1/2 and u_min/u_max per agent instead of per launch: sc_cbfqp_solve_batch_agents (further down).
  */
 int sc_cbfqp_solve_batch(const sc_cbfqp_params* params, int64_t B, int32_t K,
                          const void* X, const void* u_ref, const void* obs,
@@ -731,7 +732,8 @@ typedef struct sc_tracking_params {
  * whose ret != 0 is frozen); ret_step [B] in/out: step_offset + step index inside the launch at which
  * ret turned non-zero (initialise to -1; untouched for agents that were already frozen); traj_X [n_steps,B,4], traj_U [n_steps,B,2] optional (NULL to skip):
  * state AFTER each step and the input applied (rows of frozen agents repeat their last state).
- * The same loop with the optimal-decay CBF-QP as its position controller: sc_tracking_od_rollout_batch below.
+ * The same loop with the optimal-decay CBF-QP as its position controller: sc_tracking_od_rollout_batch below; with robot and CBF
+ * parameters per agent (sweeps, heterogeneous teams): sc_tracking_rollout_batch_agents below.
  */
 int sc_tracking_rollout_batch(const sc_tracking_params* params, int64_t B, int32_t M,
                               void* X, const void* waypoints, const int32_t* n_wp,
@@ -766,6 +768,46 @@ int sc_tracking_od_rollout_batch(const sc_tracking_od_params* params, int64_t B,
                                  int32_t* wp_index, int32_t* state_machine, void* goal,
                                  void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
                                  void* traj_X, void* traj_U, void* omega, void* min_h, void* traj_omega, void* stream);
+
+/* ---- per-agent robot and CBF parameters (parameter sweeps, heterogeneous teams) ---------------------------
+ * sc_cbfqp_solve_batch and sc_tracking_rollout_batch take robot_spec / cbf_param once for the whole batch.  Their `_agents`
+ * siblings read the quantities below per agent from `agent_params`: DEVICE memory, always double whatever io_dtype is, laid out
+ * [SC_AGENT_PARAM_COLS][B] (one column per quantity, agents contiguous: a wave's loads coalesce).  Everything else -- model, dt,
+ * cbf_mode, num_constraints, the k_* gains, rear_ax_dist, wheel_base, delta_max, mass, enable_rotation, dyn_obs -- stays
+ * launch-uniform and is read from the struct; the struct's own copies of the tabled quantities are not read.  The kernels form their
+ * derived constants from an agent's columns with the expressions the scalar path uses (csrc/sc_models.hpp: make_consts), so a table
+ * whose rows all equal the struct's values gives the scalar entry point's bits in the same kernel template.  Arithmetic is f64
+ * (compute_dtype is not read), storage f32 or f64.  The device cannot check a table cheaply: the caller validates it (finite
+ * values, u_min <= u_max, v_min <= v_max), as safe_control_amd/robots/spec.py: agent_param_table does.                          */
+#define SC_AP_RADIUS  0   /* robot radius: barrier rows and collision tests   (replaces qp.robot_radius)                   */
+#define SC_AP_ALPHA1  1   /* alpha1 (rel-degree 2) or alpha                   (qp.alpha1)                                  */
+#define SC_AP_ALPHA2  2   /* alpha2 (rel-degree 2) or 0                       (qp.alpha2)                                  */
+#define SC_AP_U_MIN0  3   /* input box, as cbf_qp.py:54-79 derives it per model (qp.u_min / qp.u_max); U_MAX0 is also the   */
+#define SC_AP_U_MIN1  4   /*   a_max of DoubleIntegrator2D's nominal controller                                           */
+#define SC_AP_U_MAX0  5
+#define SC_AP_U_MAX1  6
+#define SC_AP_V_MAX   7   /* nominal-input saturation, upper end of the bicycle's speed clip (v_max); rollout only         */
+#define SC_AP_V_MIN   8   /* lower end of the bicycle's speed clip (v_min); rollout only                                   */
+#define SC_AP_REACHED 9   /* reached_threshold; rollout only                                                              */
+#define SC_AGENT_PARAM_COLS 10
+
+/* sc_cbfqp_solve_batch with per-agent parameters.  The 4-state models (Quad2D, state_dim 6: SC_ERR_INVALID_ARGUMENT); one QP per
+ * lane (the generic kernel of csrc/cbf_qp_kernel.hpp) at every B and K.  Refused with SC_ERR_INVALID_ARGUMENT before any device
+ * call: agent_params == NULL, B <= 0, K outside [1, SC_CBFQP_MAX_OBS], and what sc_cbfqp_solve_batch refuses.                */
+int sc_cbfqp_solve_batch_agents(const sc_cbfqp_params* params, int64_t B, int32_t K,
+                                const void* X, const void* u_ref, const void* obs,
+                                const int32_t* n_obs, const double* agent_params,
+                                void* u_out, int32_t* status_out, void* h_out,
+                                void* stream);
+
+/* sc_tracking_rollout_batch with per-agent parameters: same models, same kernels (lane-per-agent and cooperative) and the same
+ * dispatch between them.  Refused with SC_ERR_INVALID_ARGUMENT before any device call: agent_params == NULL, B <= 0,
+ * num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS], and what sc_tracking_rollout_batch refuses.                       */
+int sc_tracking_rollout_batch_agents(const sc_tracking_params* params, int64_t B, int32_t M,
+                                     void* X, const void* waypoints, const int32_t* n_wp,
+                                     int32_t* wp_index, int32_t* state_machine, void* goal,
+                                     void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step,
+                                     void* traj_X, void* traj_U, const double* agent_params, void* stream);
 
 /* The fused loop for Quad2D (robots/quad2D.py; examples/test_tracking.py --model quad --algo cbf_qp, dynamic_env/main.py:314) under the
  * two QP position controllers (kernel csrc/tracking_quad_qp.hip).  One launch = n_steps iterations of control_step, one agent per lane:

@@ -20,7 +20,7 @@ from .position_control.optimal_decay_cbf_qp import OptimalDecayCBFQP, BatchedOpt
 from .position_control.optimal_decay_mpc_cbf import OptimalDecayMPCCBF, BatchedOptimalDecayMPCCBF  # noqa: F401
 from .position_control.optimal_decay_mpc_cbf_gn import OptimalDecayGnMPCCBF, BatchedOptimalDecayGnMPCCBF  # noqa: F401
 from .shielding import MPS, BatchedShield, Gatekeeper  # noqa: F401
-from .robots.spec import RobotHandle, complete_robot_spec  # noqa: F401
+from .robots.spec import RobotHandle, agent_param_table, complete_robot_spec, stack_robot_specs, unstack_robot_specs  # noqa: F401
 from .tracking import BatchedTrackingController, BatchedFleetTrackingController, BatchedSensingTrackingController  # noqa: F401
 from .tracking import BatchedSensingMPCTrackingController  # noqa: F401
 

@@ -33,6 +33,10 @@ MODEL_IDS = {
 
 STATE_DIM = {"Quad2D": 6}          # everything else: 4
 
+# per-agent parameter table of the `_agents` entry points: float64 [AGENT_PARAM_COLS, B] on the device (SC_AP_* of the header)
+AP_RADIUS, AP_ALPHA1, AP_ALPHA2, AP_U_MIN0, AP_U_MIN1, AP_U_MAX0, AP_U_MAX1, AP_V_MAX, AP_V_MIN, AP_REACHED = range(10)
+AGENT_PARAM_COLS = 10
+
 
 class CbfQpParams(C.Structure):
     """Mirror of ``sc_cbfqp_params``."""
@@ -441,6 +445,8 @@ SYMBOLS = {
     "sc_drift_shield_step_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64] + [C.c_void_p] * 13),
     "sc_drift_shield_rollout_batch": (C.c_int, [C.POINTER(DriftShieldParams), C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 11),
     "sc_tracking_rollout_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),
+    "sc_tracking_rollout_batch_agents": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 14),
+    "sc_cbfqp_solve_batch_agents": (C.c_int, [C.POINTER(CbfQpParams), C.c_int64, C.c_int32] + [C.c_void_p] * 9),
     "sc_tracking_od_rollout_batch": (C.c_int, [C.POINTER(TrackingOdParams), C.c_int64, C.c_int32] + [C.c_void_p] * 16),
     "sc_tracking_quad2d_rollout_batch": (C.c_int, [C.POINTER(TrackingQuad2dParams), C.c_int64, C.c_int32] + [C.c_void_p] * 16),
     "sc_tracking_select_batch": (C.c_int, [C.POINTER(TrackingParams), C.c_int64, C.c_int32] + [C.c_void_p] * 13),

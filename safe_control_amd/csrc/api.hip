@@ -39,6 +39,12 @@ hipError_t tracking_apply_launch(const sc_tracking_params& p, long long B, int M
 hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                            int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                            void* tX, void* tU, hipStream_t stream);
+hipError_t tracking_agents_launch(const sc_tracking_params& p, const double* agent_params, long long B, int M, void* X,
+                                  const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, void* table, void* u_last,
+                                  int* ret, int* ret_step, void* tX, void* tU, hipStream_t stream);
+hipError_t cbfqp_agents_launch(const sc_cbfqp_params& p, const double* agent_params, long long B, int K, const void* X,
+                               const void* u_ref, const void* obs, const int* n_obs, void* u_out, int* status, void* h_out,
+                               hipStream_t stream);
 hipError_t tracking_od_launch(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                               int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                               void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream);
@@ -906,6 +912,26 @@ int sc_cbfqp_solve_batch(const sc_cbfqp_params* params, int64_t B, int32_t K, co
     return SC_OK;
 }
 
+int sc_cbfqp_solve_batch_agents(const sc_cbfqp_params* params, int64_t B, int32_t K, const void* X, const void* u_ref,
+                                const void* obs, const int32_t* n_obs, const double* agent_params, void* u_out,
+                                int32_t* status_out, void* h_out, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!agent_params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "agent_params is NULL");
+    if (B <= 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B <= 0 (the per-agent table has one column entry per agent)");
+    if (K > SC_CBFQP_MAX_OBS) return sc::fail(SC_ERR_INVALID_ARGUMENT, "K exceeds SC_CBFQP_MAX_OBS");
+    if (params->model_id == SC_MODEL_QUAD2D || params->state_dim == 6)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "per-agent parameters are built for the 4-state models: Quad2D is not served");
+    int rc = sc::check_cbfqp(params, B, K, X, u_ref, obs, u_out, status_out);
+    if (rc != SC_OK) return rc;
+    if (sc::misaligned(agent_params, 8)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "agent_params must be 8-byte aligned");
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::cbfqp_agents_launch(*params, agent_params, (long long)B, (int)K, X, u_ref, obs, n_obs, u_out, status_out,
+                                           h_out, (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "per-agent cbfqp kernel launch");
+    return SC_OK;
+}
+
 int sc_cbfqp_solve_batch_host(const sc_cbfqp_params* params, int64_t B, int32_t K, const void* X,
                               const void* u_ref, const void* obs, const int32_t* n_obs, void* u_out,
                               int32_t* status_out, void* h_out, int device) {
@@ -1382,35 +1408,68 @@ int sc_odmpccbf_solve_batch_host(const sc_odmpccbf_params* params, int64_t B, in
     return rc;
 }
 
+namespace sc {
+// what sc_tracking_rollout_batch and its per-agent sibling refuse alike, before the launch
+static int check_tracking_rollout(const sc_tracking_params* params, int64_t B, int32_t M, const void* X, const void* waypoints,
+                                  const void* n_wp, const void* wp_index, const void* state_machine, const void* goal,
+                                  const void* obs_table, const void* u_last, const void* ret, const void* ret_step) {
+    if (!params) return fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    const sc_cbfqp_params* q = &params->qp;
+    if (B < 0 || M < 0) return fail(SC_ERR_INVALID_ARGUMENT, "B < 0 or M < 0");
+    const bool integrator = q->model_id == SC_MODEL_SINGLE_INTEGRATOR2D || q->model_id == SC_MODEL_DOUBLE_INTEGRATOR2D;
+    if (q->model_id < 0 || (q->model_id > SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF && q->model_id != SC_MODEL_UNICYCLE2D && !integrator))
+        return fail(SC_ERR_UNSUPPORTED, "the fused rollout is built for the unicycle / bicycle / integrator models");
+    if (integrator && params->enable_rotation)
+        return fail(SC_ERR_UNSUPPORTED, "the integrators' rotate state needs an attitude controller: enable_rotation must be 0");
+    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
+        return fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
+    if (params->num_constraints < 1 || params->num_constraints > SC_TRACKING_MAX_CONSTRAINTS)
+        return fail(SC_ERR_UNSUPPORTED, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
+    if (params->n_steps < 0 || params->max_waypoints < 1) return fail(SC_ERR_INVALID_ARGUMENT, "n_steps < 0 or max_waypoints < 1");
+    if (!(q->dt > 0)) return fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0");
+    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && q->model_id != SC_MODEL_UNICYCLE2D && !integrator &&
+        (!(q->rear_ax_dist > 0) || !(params->wheel_base > 0)))
+        return fail(SC_ERR_INVALID_ARGUMENT, "rear_ax_dist and wheel_base must be > 0 for the KinematicBicycle2D family");
+    if ((size_t)M * 7 * 8 > 160 * 1024) return fail(SC_ERR_UNSUPPORTED, "obstacle table does not fit the LDS");
+    if (B > 0 && (!X || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !u_last || !ret || !ret_step || (M > 0 && !obs_table)))
+        return fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    return SC_OK;
+}
+}  // namespace sc
+
 int sc_tracking_rollout_batch(const sc_tracking_params* params, int64_t B, int32_t M, void* X, const void* waypoints,
                               const int32_t* n_wp, int32_t* wp_index, int32_t* state_machine, void* goal,
                               void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step, void* traj_X,
                               void* traj_U, void* stream) {
     sc::DeviceGuard on_device(stream, X);
-    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
-    const sc_cbfqp_params* q = &params->qp;
-    if (B < 0 || M < 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B < 0 or M < 0");
-    const bool integrator = q->model_id == SC_MODEL_SINGLE_INTEGRATOR2D || q->model_id == SC_MODEL_DOUBLE_INTEGRATOR2D;
-    if (q->model_id < 0 || (q->model_id > SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF && q->model_id != SC_MODEL_UNICYCLE2D && !integrator))
-        return sc::fail(SC_ERR_UNSUPPORTED, "the fused rollout is built for the unicycle / bicycle / integrator models");
-    if (integrator && params->enable_rotation)
-        return sc::fail(SC_ERR_UNSUPPORTED, "the integrators' rotate state needs an attitude controller: enable_rotation must be 0");
-    if (q->io_dtype != SC_DTYPE_F32 && q->io_dtype != SC_DTYPE_F64)
-        return sc::fail(SC_ERR_INVALID_ARGUMENT, "io_dtype must be SC_DTYPE_F32 or SC_DTYPE_F64");
-    if (params->num_constraints < 1 || params->num_constraints > SC_TRACKING_MAX_CONSTRAINTS)
-        return sc::fail(SC_ERR_UNSUPPORTED, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
-    if (params->n_steps < 0 || params->max_waypoints < 1) return sc::fail(SC_ERR_INVALID_ARGUMENT, "n_steps < 0 or max_waypoints < 1");
-    if (!(q->dt > 0)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "dt must be > 0");
-    if (q->model_id != SC_MODEL_DYNAMIC_UNICYCLE2D && q->model_id != SC_MODEL_UNICYCLE2D && !integrator &&
-        (!(q->rear_ax_dist > 0) || !(params->wheel_base > 0)))
-        return sc::fail(SC_ERR_INVALID_ARGUMENT, "rear_ax_dist and wheel_base must be > 0 for the KinematicBicycle2D family");
-    if ((size_t)M * 7 * 8 > 160 * 1024) return sc::fail(SC_ERR_UNSUPPORTED, "obstacle table does not fit the LDS");
-    if (B > 0 && (!X || !waypoints || !n_wp || !wp_index || !state_machine || !goal || !u_last || !ret || !ret_step || (M > 0 && !obs_table)))
-        return sc::fail(SC_ERR_INVALID_ARGUMENT, "NULL data pointer");
+    int rc = sc::check_tracking_rollout(params, B, M, X, waypoints, n_wp, wp_index, state_machine, goal, obs_table, u_last, ret, ret_step);
+    if (rc != SC_OK) return rc;
     if (B == 0 || params->n_steps == 0) return SC_OK;
     hipError_t e = sc::tracking_launch(*params, (long long)B, (int)M, X, waypoints, n_wp, wp_index, state_machine, goal,
                                        obs_table, u_last, ret, ret_step, traj_X, traj_U, (hipStream_t)stream);
     if (e != hipSuccess) return sc::fail_hip(e, "tracking kernel launch");
+    return SC_OK;
+}
+
+int sc_tracking_rollout_batch_agents(const sc_tracking_params* params, int64_t B, int32_t M, void* X, const void* waypoints,
+                                     const int32_t* n_wp, int32_t* wp_index, int32_t* state_machine, void* goal,
+                                     void* obs_table, void* u_last, int32_t* ret, int32_t* ret_step, void* traj_X,
+                                     void* traj_U, const double* agent_params, void* stream) {
+    // every argument is checked before the first HIP call (the device guard included)
+    if (!params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!agent_params) return sc::fail(SC_ERR_INVALID_ARGUMENT, "agent_params is NULL");
+    if (B <= 0) return sc::fail(SC_ERR_INVALID_ARGUMENT, "B <= 0 (the per-agent table has one column entry per agent)");
+    if (params->num_constraints < 1 || params->num_constraints > SC_TRACKING_MAX_CONSTRAINTS)
+        return sc::fail(SC_ERR_INVALID_ARGUMENT, "num_constraints outside [1, SC_TRACKING_MAX_CONSTRAINTS]");
+    int rc = sc::check_tracking_rollout(params, B, M, X, waypoints, n_wp, wp_index, state_machine, goal, obs_table, u_last, ret, ret_step);
+    if (rc != SC_OK) return rc;
+    if (sc::misaligned(agent_params, 8)) return sc::fail(SC_ERR_INVALID_ARGUMENT, "agent_params must be 8-byte aligned");
+    if (params->n_steps == 0) return SC_OK;
+    sc::DeviceGuard on_device(stream, X);
+    hipError_t e = sc::tracking_agents_launch(*params, agent_params, (long long)B, (int)M, X, waypoints, n_wp, wp_index,
+                                              state_machine, goal, obs_table, u_last, ret, ret_step, traj_X, traj_U,
+                                              (hipStream_t)stream);
+    if (e != hipSuccess) return sc::fail_hip(e, "per-agent tracking kernel launch");
     return SC_OK;
 }
 

@@ -21,6 +21,7 @@
 
 #include "sc_qp2.hpp"
 #include "sc_group.hpp"
+#include "sc_agent_params.hpp"
 
 namespace sc {
 
@@ -666,12 +667,16 @@ static hipError_t launch_coop(const sc_cbfqp_params& p, long long B, int K, cons
 // (r + l / P) mod K at step r, P = 32 / gcd(K, 32).  Lanes whose staged rows start on the same
 // LDS bank (stride K*7 dwords) then read different rows, which removes the 8- (K = 8) to 16-way
 // (K = 16) bank conflict of the straightforward order; the QP does not care about row order.
-template <typename TIO, typename TC, int KMAX, int MODEL>
+//
+// AGENTS (sc_cbfqp_solve_batch_agents; instantiated in cbf_qp_agents.hip): the last argument is the launch-uniform parameter struct
+// and the [SC_AGENT_PARAM_COLS][B] table instead of finished constants, and every lane builds its agent's constants from its
+// columns (sc_agent_params.hpp), issued with the state loads.  With AGENTS = false `k` is the argument itself, as before.
+template <typename TIO, typename TC, int KMAX, int MODEL, bool AGENTS = false>
 __global__ __launch_bounds__(64) void cbfqp_kernel(const TIO* __restrict__ obs, const TIO* __restrict__ X,
                                                    const TIO* __restrict__ u_ref, const int* __restrict__ n_obs,
                                                    const long long B, const int K, const int obs_shared,
                                                    TIO* __restrict__ u_out, int* __restrict__ status_out,
-                                                   TIO* __restrict__ h_out, const CbfConsts<TC> k) {
+                                                   TIO* __restrict__ h_out, const CbfQpArgs<AGENTS, TC> kargs) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     TIO* lobs = reinterpret_cast<TIO*>(smem);
 
@@ -706,6 +711,7 @@ __global__ __launch_bounds__(64) void cbfqp_kernel(const TIO* __restrict__ obs, 
     nk = !active ? K : (nk < 0 ? 0 : (nk > K ? K : nk));
     const TC ur0 = active ? TC(ur.x) : TC(0), ur1 = active ? TC(ur.y) : TC(0);
     const Agent<TC> ag = to_agent<TIO, TC, MODEL>(xs);
+    const auto& k = solve_consts<TC>(kargs, B, ag_i);
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // LDS-DMA landed (it is tracked by vmcnt)
     __syncthreads();

@@ -17,7 +17,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from ..robots.spec import complete_robot_spec
+from ..robots.spec import AGENT_SPEC_SERVED, agent_param_table, check_agent_spec, complete_robot_spec
 
 REL_DEG2_MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "DoubleIntegrator2D", "Quad2D")
 
@@ -175,9 +175,13 @@ class BatchedCBFQP:
     ``u[B,2]`` (NaN where not optimal), ``status[B] int32``, ``h[B,K]``.
     Tensors must be contiguous CUDA tensors of ``io_dtype``; the launch goes on
     the current torch stream and does not synchronise.
+
+    ``agent_spec`` (``robots.spec.stack_robot_specs``): radius, input limits and CBF gains per agent.  ``solve`` then takes a
+    batch of exactly that many agents and runs sc_cbfqp_solve_batch_agents (one QP per lane, f64 arithmetic).
     """
 
-    def __init__(self, robot_spec, dt=0.05, io_dtype="f32", compute_dtype="f64", cbf_param=None):
+    def __init__(self, robot_spec, dt=0.05, io_dtype="f32", compute_dtype="f64", cbf_param=None, agent_spec=None):
+        user_cbf_param = cbf_param
         self.robot_spec = complete_robot_spec(robot_spec)
         _check_cbfqp_model(self.robot_spec)
         self.dt = float(dt)
@@ -185,6 +189,27 @@ class BatchedCBFQP:
         self.compute_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[compute_dtype]
         self.cbf_param = cbf_param or apply_cbf_overrides(default_cbf_param(self.robot_spec["model"]), self.robot_spec)
         self._lib = _lib.load()
+        # per-agent parameters (robots/spec.py: stack_robot_specs): the [AGENT_PARAM_COLS, B] device table solve() hands to
+        # sc_cbfqp_solve_batch_agents; None: the scalar entry point, as before
+        self.agent_spec = self.agent_table = None
+        if agent_spec is not None:
+            if self.robot_spec["model"] == "Quad2D":
+                raise ValueError(f"{AGENT_SPEC_SERVED}; Quad2D has no per-agent form")
+            if compute_dtype != "f64":
+                raise ValueError("per-agent parameters: arithmetic is f64 (compute_dtype='f64'); storage may be f32 or f64")
+            lens = {len(np.atleast_1d(v)) for v in agent_spec.values()}
+            if len(lens) != 1:
+                raise ValueError("agent_spec needs at least one key, and the same number of agents under every key")
+            n_agents = lens.pop()
+            self.agent_spec = check_agent_spec(agent_spec, n_agents)
+            self._agent_host = agent_param_table(self.robot_spec, self.agent_spec, n_agents, cbf_param=user_cbf_param)
+
+    def _agent_table_on(self, device):
+        """The per-agent table on ``device`` (uploaded on first use, kept)."""
+        import torch
+        if self.agent_table is None or self.agent_table.device != device:
+            self.agent_table = torch.tensor(self._agent_host, dtype=torch.float64, device=device).contiguous()
+        return self.agent_table
 
     @property
     def torch_dtype(self):
@@ -215,6 +240,16 @@ class BatchedCBFQP:
         p = make_params(self.robot_spec, self.cbf_param, self.dt, self.robot_spec["radius"],
                         self.io_dtype, self.compute_dtype, obs_shared=shared)
         stream = torch.cuda.current_stream(X.device).cuda_stream
+        if self.agent_spec is not None:
+            tab = self._agent_table_on(X.device)
+            if tab.shape != (_lib.AGENT_PARAM_COLS, B):
+                raise ValueError(f"the per-agent table holds {tab.shape[1]} agents, X has {B}")
+            rc = self._lib.sc_cbfqp_solve_batch_agents(
+                C.byref(p), B, K, X.data_ptr(), u_ref.data_ptr(), obs.data_ptr(),
+                n_obs.data_ptr() if n_obs is not None else None, tab.data_ptr(),
+                u.data_ptr(), status.data_ptr(), h.data_ptr() if h is not None else None, stream)
+            _lib.check(rc, "sc_cbfqp_solve_batch_agents")
+            return u, status, h
         rc = self._lib.sc_cbfqp_solve_batch(
             C.byref(p), B, K, X.data_ptr(), u_ref.data_ptr(), obs.data_ptr(),
             n_obs.data_ptr() if n_obs is not None else None,

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from .. import _lib
-from ..robots.spec import complete_robot_spec
+from ..robots.spec import AGENT_SPEC_SERVED, complete_robot_spec
 from .cbf_qp import REL_DEG2_MODELS, _pad_obstacle, make_params
 
 
@@ -96,7 +96,9 @@ class OptimalDecayCBFQP:
 class BatchedOptimalDecayCBFQP:
     """``solve(X[B,4], u_ref[B,2], obs[B,7], has_obs[B]|None)`` -> ``u[B,2], omega[B,2], status[B], h[B]``."""
 
-    def __init__(self, robot_spec, dt=0.05, io_dtype="f32", compute_dtype="f64", cbf_param=None):
+    def __init__(self, robot_spec, dt=0.05, io_dtype="f32", compute_dtype="f64", cbf_param=None, agent_spec=None):
+        if agent_spec is not None:
+            raise ValueError(f"{AGENT_SPEC_SERVED}; not by 'optimal_decay_cbf_qp'")
         self.robot_spec = complete_robot_spec(robot_spec)
         self.dt = float(dt)
         self.io_dtype = {"f32": _lib.DTYPE_F32, "f64": _lib.DTYPE_F64}[io_dtype]

@@ -30,7 +30,7 @@ import numpy as np
 from . import _lib
 from .position_control.cbf_qp import apply_cbf_overrides, default_cbf_param, make_params
 from .position_control.optimal_decay_cbf_qp import apply_od_overrides, default_od_param
-from .robots.spec import complete_robot_spec
+from .robots.spec import AGENT_SPEC_SERVED, agent_param_table, check_agent_spec, complete_robot_spec
 
 
 # the four-state models of csrc/tracking_od.hip (Quad2D flies through BatchedQuadTrackingController)
@@ -46,6 +46,12 @@ TRAJ_YAW_SEEN = (((), None), ((), "int64"))                    # traj_yaw [n,B],
 
 def _wrap(a):
     return ((a + math.pi) % (2.0 * math.pi)) - math.pi
+
+
+def _refuse_agent_spec(agent_spec, who):
+    """Per-agent parameters exist for the 'cbf_qp' solve and fused loop; every other loop says so instead of ignoring them."""
+    if agent_spec is not None:
+        raise ValueError(f"{AGENT_SPEC_SERVED}; not by {who}")
 
 
 def _shared_list(waypoints):
@@ -66,6 +72,10 @@ class BatchedTrackingController:
     allowed) runs the fused rollout of csrc/tracking_od.hip; ``cbf_param`` then holds the optimal-decay parameters
     (``robot_spec`` keys cbf_alpha*, cbf_omega1/2, cbf_p_sb1/2 override them) and ``self.omega`` / ``self.min_h`` the decay
     multipliers of every agent's last solve and the smallest barrier value it met.
+
+    ``agent_spec`` (``robots.spec.stack_robot_specs``; 'cbf_qp' only): radius, input and speed limits, CBF gains and
+    ``reached_threshold`` per agent, read by the fused rollout from the device table ``agent_table [AGENT_PARAM_COLS, B]``
+    (sc_tracking_rollout_batch_agents); ``fov_angle`` per agent decides each agent's first state in ``set_waypoints`` on the host.
     """
 
     def __new__(cls, X0, robot_spec, *args, **kwargs):
@@ -86,9 +96,11 @@ class BatchedTrackingController:
     _nominal_gains = True
 
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None,
-                 dyn_obs=False, io_dtype="f64", device="cuda:0"):
+                 dyn_obs=False, io_dtype="f64", device="cuda:0", agent_spec=None):
         controller_type = controller_type or {"pos": "cbf_qp"}
         self.pos_controller_type = controller_type.get("pos", "cbf_qp")           # tracking.py:140-154
+        if self.pos_controller_type != "cbf_qp":
+            _refuse_agent_spec(agent_spec, f"position controller {self.pos_controller_type!r}")
         if self.pos_controller_type not in ("cbf_qp", "optimal_decay_cbf_qp", "mpc_cbf", "optimal_decay_mpc_cbf"):
             raise ValueError("position controllers of the batched loop: 'cbf_qp', 'optimal_decay_cbf_qp' (fused rollouts), 'mpc_cbf', "
                              "'optimal_decay_mpc_cbf' (select / solve / apply per step)")
@@ -116,7 +128,10 @@ class BatchedTrackingController:
             X0 = np.hstack([X0[:, :nst], np.zeros((X0.shape[0], 4 - nst))])
         elif X0.shape[1] == 3:                                 # tracking.py:66-68: initial speed 0
             X0 = np.hstack([X0, np.zeros((X0.shape[0], 1))])
+        agent_host = self._agent_columns(agent_spec, X0.shape[0])       # refuses a wrong length before the first device tensor
         self._allocate(X0, obs)
+        if agent_host is not None:
+            self.agent_table = self.torch.tensor(agent_host, dtype=self.torch.float64, device=self.device).contiguous()
         if self.od_qp or self.pos_controller_type == "cbf_qp":
             return
         if self.dyn_obs:
@@ -166,7 +181,22 @@ class BatchedTrackingController:
         self.reached_threshold = float(self.robot_spec.get("reached_threshold", 0.3))    # tracking.py:49-54
         self.rotation_threshold = 0.1                                                    # tracking.py:46
         self.fov_angle = math.radians(float(self.robot_spec.get("fov_angle", 70.0)))      # robots/robot.py:53-54
+        # per-agent parameters (agent_spec): the device table of the `_agents` rollout and, for set_waypoints, every agent's own
+        # reached_threshold and camera angle; None: one robot_spec for the whole batch
+        self.agent_spec = self.agent_table = self.agent_reached = self.agent_fov = None
         self._lib = _lib.load()
+
+    def _agent_columns(self, agent_spec, B):
+        """The host half of ``agent_spec``: checks it against the batch, keeps every agent's reached_threshold and fov_angle for
+        ``set_waypoints`` and returns the ``[AGENT_PARAM_COLS, B]`` table (None without ``agent_spec``)."""
+        if agent_spec is None:
+            return None
+        self.agent_spec = check_agent_spec(agent_spec, B)
+        table = agent_param_table(self.robot_spec, self.agent_spec, B)
+        self.agent_reached = table[_lib.AP_REACHED].copy()
+        fov = self.agent_spec.get("fov_angle", np.full(B, math.nan))
+        self.agent_fov = np.where(np.isnan(fov), self.fov_angle, np.radians(fov))
+        return table
 
     def _allocate(self, X0, obs, cbf_qp=True):
         """The device half: the state ``X0 [B,nx]`` as unpacked by the class, the per-agent tensors, the obstacle table and the
@@ -240,6 +270,9 @@ class BatchedTrackingController:
         X = self.X.double().cpu().numpy()
         npos, cols = self.npos, self.wp_cols
         yaw = self._headings(X)
+        # every agent's own reached_threshold and camera angle under agent_spec, the spec's otherwise
+        reached = self.agent_reached if self.agent_reached is not None else np.full(self.B, self.reached_threshold)
+        fov_angle = self.agent_fov if self.agent_fov is not None else np.full(self.B, self.fov_angle)
         lists = [np.asarray(waypoints, dtype=np.float64)] * self.B if _shared_list(waypoints) else \
             [np.asarray(w, dtype=np.float64) for w in waypoints]
         filt = []
@@ -250,7 +283,7 @@ class BatchedTrackingController:
             if len(wp) >= 2:                                   # filter_waypoints
                 aug = np.vstack((X[i, :npos], wp[:, :npos]))
                 dist = np.linalg.norm(np.diff(aug, axis=0), axis=1)
-                mask = np.concatenate(([False], dist >= self.reached_threshold))
+                mask = np.concatenate(([False], dist >= reached[i]))
                 wp = aug[mask]
             row = np.zeros((len(wp), cols))
             row[:, :npos] = wp[:, :npos]
@@ -268,13 +301,13 @@ class BatchedTrackingController:
             # update_goal with state machine 'idle' (tracking.py:517-535)
             g = None
             if len(w) > 0:
-                if np.linalg.norm(X[i, :2] - w[0, :2]) < self.reached_threshold:
+                if np.linalg.norm(X[i, :2] - w[0, :2]) < reached[i]:
                     idx[i] = 1
                 if idx[i] < len(w):
                     g = w[idx[i]]
             if g is not None:                                   # tracking.py:214-226
                 ang = math.atan2(g[1] - X[i, 1], g[0] - X[i, 0])
-                in_fov = yaw is None or abs(_wrap(ang - yaw[i])) <= self.fov_angle / 2
+                in_fov = yaw is None or abs(_wrap(ang - yaw[i])) <= fov_angle[i] / 2
                 if in_fov or self.robot_spec["exploration"]:
                     sm[i] = _lib.SM_TRACK if in_fov else _lib.SM_ROTATE
                     goal[i, :cols] = g
@@ -384,6 +417,9 @@ class BatchedTrackingController:
             return self._control_step_split(n, record)
         if self.od_qp:
             return self._control_step_od(n, record)
+        if self.agent_table is not None:                            # the table goes in behind traj_U
+            return self._rollout(self._lib.sc_tracking_rollout_batch_agents, (C.byref(self._tracking_params(n)),), n, record,
+                                 after=(self.agent_table.data_ptr(),))
         return self._rollout(self._lib.sc_tracking_rollout_batch, (C.byref(self._tracking_params(n)),), n, record)
 
     def _control_step_od(self, n, record):
@@ -514,7 +550,8 @@ class BatchedQuadTrackingController(BatchedTrackingController):
     _nominal_gains = False
 
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, dyn_obs=False,
-                 io_dtype="f64", device="cuda:0"):
+                 io_dtype="f64", device="cuda:0", agent_spec=None):
+        _refuse_agent_spec(agent_spec, "the Quad2D / Quad3D / VTOL2D loops")
         controller_type = controller_type or {"pos": "mpc_cbf"}
         self.pos_controller_type = controller_type.get("pos", "mpc_cbf")
         model = robot_spec["model"]
@@ -684,8 +721,9 @@ class BatchedSensingTrackingController(BatchedTrackingController):
     POS_REFUSAL = "the sensing loop's position controller is 'cbf_qp' here ('mpc_cbf': BatchedSensingMPCTrackingController)"
 
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, unknown_obs=None,
-                 io_dtype="f64", device="cuda:0"):
+                 io_dtype="f64", device="cuda:0", agent_spec=None):
         # every argument is checked here, before the base class creates the first device tensor
+        _refuse_agent_spec(agent_spec, "the sensing loops")
         controller_type = dict(controller_type or {})
         robot_spec = dict(robot_spec)
         model = robot_spec.get("model")
@@ -854,8 +892,9 @@ class BatchedFleetTrackingController(BatchedTrackingController):
     MODELS = ("DynamicUnicycle2D", "KinematicBicycle2D", "KinematicBicycle2D_C3BF", "KinematicBicycle2D_DPCBF")
 
     def __init__(self, X0, robot_spec, controller_type=None, dt=0.05, enable_rotation=True, obs=None, dyn_obs=False,
-                 neighbours=16, num_constraints=None, io_dtype="f64", device="cuda:0"):
+                 neighbours=16, num_constraints=None, io_dtype="f64", device="cuda:0", agent_spec=None):
         from . import sharding
+        _refuse_agent_spec(agent_spec, "the fleet step")
         robot_spec = dict(robot_spec)
         if robot_spec.get("model", "DynamicUnicycle2D") not in self.MODELS:
             raise ValueError(f"the fleet step supports {', '.join(self.MODELS)}; not {robot_spec.get('model')!r}")
