@@ -199,87 +199,42 @@ hipError_t advance_obstacle_table_launch(bool f32, void* table, int M, int n_ste
     return hipGetLastError();
 }
 
-template <typename TIO, int MODEL>
-static hipError_t launch_select_m(const sc_tracking_params& p, long long B, int M, const void* X, const void* wps,
-                                  const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const int* ret,
-                                  void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    auto go = [&](auto kern) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, (const TIO*)X, (const TIO*)wps, n_wp, wp_index,
-                           sm, (TIO*)goal, (const TIO*)table, ret, (TIO*)obs_out, (TIO*)goal_out, (TIO*)u_ref_out, track_out);
-        return hipGetLastError();
-    };
-    if (p.num_constraints <= 8) return go(tracking_select_kernel<TIO, double, 8, MODEL>);
-    return go(tracking_select_kernel<TIO, double, 16, MODEL>);
-}
-
-template <typename TIO>
-static hipError_t launch_select_t(const sc_tracking_params& p, long long B, int M, const void* X, const void* wps,
-                                  const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const int* ret,
-                                  void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    if (p.qp.model_id == SC_MODEL_DYNAMIC_UNICYCLE2D)
-        return launch_select_m<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    if (p.qp.model_id == SC_MODEL_UNICYCLE2D)
-        return launch_select_m<TIO, SC_MODEL_UNICYCLE2D>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    if (p.qp.model_id == SC_MODEL_SINGLE_INTEGRATOR2D)
-        return launch_select_m<TIO, SC_MODEL_SINGLE_INTEGRATOR2D>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    if (p.qp.model_id == SC_MODEL_DOUBLE_INTEGRATOR2D)
-        return launch_select_m<TIO, SC_MODEL_DOUBLE_INTEGRATOR2D>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    return launch_select_m<TIO, SC_MODEL_KINEMATIC_BICYCLE2D>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-}
-
 hipError_t tracking_select_launch(const sc_tracking_params& p, long long B, int M, const void* X, const void* wps,
                                   const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const int* ret,
                                   void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    if (p.qp.io_dtype == SC_DTYPE_F32)
-        return launch_select_t<float>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    return launch_select_t<double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-}
-
-template <typename TIO>
-static hipError_t launch_apply_t(const sc_tracking_params& p, long long B, int M, int step_index, void* X, const int* sm,
-                                 const void* goal, const void* table, const void* u, const int* u_status, void* u_last,
-                                 int* ret, int* ret_step, hipStream_t stream) {
     const unsigned blocks = (unsigned)((B + 63) / 64);
     const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    auto go = [&](auto kern) {
-        if (lds > 64 * 1024) {
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e != hipSuccess) return e;
-        }
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, step_index, (TIO*)X, sm, (const TIO*)goal,
-                           (const TIO*)table, (const TIO*)u, u_status, (TIO*)u_last, ret, ret_step);
-        return hipGetLastError();
-    };
-    if (p.qp.model_id == SC_MODEL_DYNAMIC_UNICYCLE2D) return go(tracking_apply_kernel<TIO, double, SC_MODEL_DYNAMIC_UNICYCLE2D>);
-    if (p.qp.model_id == SC_MODEL_UNICYCLE2D) return go(tracking_apply_kernel<TIO, double, SC_MODEL_UNICYCLE2D>);
-    if (p.qp.model_id == SC_MODEL_SINGLE_INTEGRATOR2D) return go(tracking_apply_kernel<TIO, double, SC_MODEL_SINGLE_INTEGRATOR2D>);
-    if (p.qp.model_id == SC_MODEL_DOUBLE_INTEGRATOR2D) return go(tracking_apply_kernel<TIO, double, SC_MODEL_DOUBLE_INTEGRATOR2D>);
-    return go(tracking_apply_kernel<TIO, double, SC_MODEL_KINEMATIC_BICYCLE2D>);
+    return dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_DYNAMIC_UNICYCLE2D, SC_MODEL_UNICYCLE2D, SC_MODEL_SINGLE_INTEGRATOR2D,
+                                 SC_MODEL_DOUBLE_INTEGRATOR2D, SC_MODEL_KINEMATIC_BICYCLE2D>(p.qp.model_id, [&](auto model) {
+            auto go = [&](auto kmax) {
+                return launch(tracking_select_kernel<tag_t<decltype(tio)>, double, decltype(kmax)::value, decltype(model)::value>, blocks, 64,
+                              lds, stream, p, B, M, X, wps, n_wp, wp_index, sm, goal, table, ret, obs_out, goal_out, u_ref_out, track_out);
+            };
+            if (p.num_constraints <= 8) return go(int_tag<8>{});
+            return go(int_tag<16>{});
+        });
+    });
 }
 
 hipError_t tracking_apply_launch(const sc_tracking_params& p, long long B, int M, int step_index, void* X, const int* sm,
                                  const void* goal, const void* table, const void* u, const int* u_status, void* u_last,
                                  int* ret, int* ret_step, hipStream_t stream) {
-    if (p.qp.io_dtype == SC_DTYPE_F32)
-        return launch_apply_t<float>(p, B, M, step_index, X, sm, goal, table, u, u_status, u_last, ret, ret_step, stream);
-    return launch_apply_t<double>(p, B, M, step_index, X, sm, goal, table, u, u_status, u_last, ret, ret_step, stream);
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
+    return dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_DYNAMIC_UNICYCLE2D, SC_MODEL_UNICYCLE2D, SC_MODEL_SINGLE_INTEGRATOR2D,
+                                 SC_MODEL_DOUBLE_INTEGRATOR2D, SC_MODEL_KINEMATIC_BICYCLE2D>(p.qp.model_id, [&](auto model) {
+            return launch(tracking_apply_kernel<tag_t<decltype(tio)>, double, decltype(model)::value>, blocks, 64, lds, stream, p, B, M,
+                          step_index, X, sm, goal, table, u, u_status, u_last, ret, ret_step);
+        });
+    });
 }
 
 hipError_t tracking_launch(const sc_tracking_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                            int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                            void* tX, void* tU, hipStream_t stream) {
-    // closed loops amplify rounding: arithmetic is always f64 here; storage follows io_dtype
-    const bool f32 = p.qp.io_dtype == SC_DTYPE_F32;
-    hipError_t e = f32 ? launch_track_m<float, double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream)
-                       : launch_track_m<double, double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
-    if (e != hipSuccess || !p.dyn_obs || M == 0) return e;
-    return advance_obstacle_table_launch(f32, table, M, p.n_steps, p.qp.dt, stream);
+    return launch_track<false>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
 }
 
 // ======================================================================================
@@ -519,64 +474,26 @@ __global__ __launch_bounds__(64) void tracking_fleet_kernel(
     }
 }
 
-template <typename TIO, typename TC, int G, int MODEL>
-static hipError_t launch_fleet(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
-                               const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
-                               const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream) {
-    constexpr int APW = 64 / G;
-    const unsigned blocks = (unsigned)((B + APW - 1) / APW);
-    const size_t lds = ((size_t)M * 7 + (size_t)APW * K_nb * 7 + 1) * sizeof(TC) + 64 * sizeof(int);
-    hipLaunchKernelGGL((tracking_fleet_kernel<TIO, TC, G, MODEL>), dim3(blocks), dim3(64), lds, stream, p, B, M, K_nb, step_index,
-                       (TIO*)X, (TIO*)X_pub, (const TIO*)wps, n_wp, wp_index, sm, (TIO*)goal, (const TIO*)table, (const TIO*)nb_rows,
-                       (TIO*)u_last, ret, ret_step, cause, (TIO*)min_sep);
-    return hipGetLastError();
-}
-
-template <typename TIO, int MODEL>
-static hipError_t launch_fleet_g(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
-                                 const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
-                                 const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream) {
-    if (p.num_constraints <= 8 && M + K_nb <= 32)
-        return launch_fleet<TIO, double, 8, MODEL>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table, nb_rows,
-                                                   u_last, ret, ret_step, cause, min_sep, stream);
-    return launch_fleet<TIO, double, 16, MODEL>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table, nb_rows,
-                                                u_last, ret, ret_step, cause, min_sep, stream);
-}
-
-template <typename TIO>
-static hipError_t launch_fleet_m(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
-                                 const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
-                                 const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream) {
-    switch (p.qp.model_id) {
-        case SC_MODEL_DYNAMIC_UNICYCLE2D:
-            return launch_fleet_g<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table,
-                                                                    nb_rows, u_last, ret, ret_step, cause, min_sep, stream);
-        case SC_MODEL_KINEMATIC_BICYCLE2D:
-            return launch_fleet_g<TIO, SC_MODEL_KINEMATIC_BICYCLE2D>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table,
-                                                                     nb_rows, u_last, ret, ret_step, cause, min_sep, stream);
-        case SC_MODEL_KINEMATIC_BICYCLE2D_C3BF:
-            return launch_fleet_g<TIO, SC_MODEL_KINEMATIC_BICYCLE2D_C3BF>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal,
-                                                                          table, nb_rows, u_last, ret, ret_step, cause, min_sep, stream);
-        default:
-            return launch_fleet_g<TIO, SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal,
-                                                                           table, nb_rows, u_last, ret, ret_step, cause, min_sep, stream);
-    }
-}
-
 hipError_t tracking_fleet_launch(const sc_tracking_params& p, long long B, int M, int K_nb, int step_index, void* X, void* X_pub,
                                  const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, void* table,
                                  const void* nb_rows, void* u_last, int* ret, int* ret_step, int* cause, void* min_sep, hipStream_t stream) {
     // arithmetic in f64 (closed loops amplify rounding), storage follows io_dtype -- as tracking_launch
-    const bool f32 = p.qp.io_dtype == SC_DTYPE_F32;
-    hipError_t e = f32 ? launch_fleet_m<float>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table, nb_rows,
-                                               u_last, ret, ret_step, cause, min_sep, stream)
-                       : launch_fleet_m<double>(p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm, goal, table, nb_rows,
-                                                u_last, ret, ret_step, cause, min_sep, stream);
+    hipError_t e = dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_DYNAMIC_UNICYCLE2D, SC_MODEL_KINEMATIC_BICYCLE2D, SC_MODEL_KINEMATIC_BICYCLE2D_C3BF,
+                                 SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF>(p.qp.model_id, [&](auto model) {
+            auto go = [&](auto g) {
+                constexpr int G = decltype(g)::value, APW = 64 / G;
+                const size_t lds = ((size_t)M * 7 + (size_t)APW * K_nb * 7 + 1) * sizeof(double) + 64 * sizeof(int);
+                return launch<false>(tracking_fleet_kernel<tag_t<decltype(tio)>, double, G, decltype(model)::value>,
+                                     (unsigned)((B + APW - 1) / APW), 64, lds, stream, p, B, M, K_nb, step_index, X, X_pub, wps, n_wp, wp_index, sm,
+                                     goal, table, nb_rows, u_last, ret, ret_step, cause, min_sep);
+            };
+            if (p.num_constraints <= 8 && M + K_nb <= 32) return go(int_tag<8>{});
+            return go(int_tag<16>{});
+        });
+    });
     if (e != hipSuccess || !p.dyn_obs || M == 0) return e;
-    const unsigned blocks = (unsigned)((M + 255) / 256);
-    if (f32) hipLaunchKernelGGL(advance_obstacle_table_kernel<float>, dim3(blocks), dim3(256), 0, stream, (float*)table, M, 1, p.qp.dt);
-    else hipLaunchKernelGGL(advance_obstacle_table_kernel<double>, dim3(blocks), dim3(256), 0, stream, (double*)table, M, 1, p.qp.dt);
-    return hipGetLastError();
+    return advance_obstacle_table_launch(p.qp.io_dtype == SC_DTYPE_F32, table, M, 1, p.qp.dt, stream);
 }
 
 }  // namespace sc

@@ -13,11 +13,7 @@ hipError_t tracking_agents_launch(const sc_tracking_params& p, const double* age
     TrackingAgentsArgs a;
     static_cast<sc_tracking_params&>(a) = p;
     a.agent_params = agent_params;
-    const bool f32 = p.qp.io_dtype == SC_DTYPE_F32;
-    hipError_t e = f32 ? launch_track_m<float, double, true>(a, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream)
-                       : launch_track_m<double, double, true>(a, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
-    if (e != hipSuccess || !p.dyn_obs || M == 0) return e;
-    return advance_obstacle_table_launch(f32, table, M, p.n_steps, p.qp.dt, stream);
+    return launch_track<true>(a, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
 }
 
 }  // namespace sc

@@ -13,6 +13,7 @@
 #include "sc_group.hpp"
 #include "tracking_common.hpp"
 #include "sc_agent_params.hpp"
+#include "sc_dispatch.hpp"
 
 namespace sc {
 
@@ -482,72 +483,48 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(coop_min_wav
     }
 }
 
-// ---- host-side dispatch, one copy for both parameter sources -----------------------------------------------------
-template <typename TIO, typename TC, int G, int MODEL, bool AGENTS>
-static hipError_t launch_track_coop(const TrackingArgs<AGENTS>& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                    int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
-                                    void* tX, void* tU, hipStream_t stream) {
-    constexpr int APW = 64 / G;
-    const unsigned blocks = (unsigned)((B + APW - 1) / APW);
-    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(TC) + 64 * sizeof(int);
-    auto kern = tracking_coop_kernel<TIO, TC, G, MODEL, AGENTS>;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, (TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                       (TIO*)goal, (TIO*)table, (TIO*)u_last, ret, ret_step, (TIO*)tX, (TIO*)tU);
-    return hipGetLastError();
-}
+// stream-ordered follow-up of a rollout over a moving table (tracking.hip)
+hipError_t advance_obstacle_table_launch(bool f32, void* table, int M, int n_steps, double dt, hipStream_t stream);
 
-template <typename TIO, typename TC, int KMAX, int MODEL, bool AGENTS>
+// ---- host-side dispatch, one copy for both parameter sources -----------------------------------------------------
+// Storage follows io_dtype; closed loops amplify rounding, so arithmetic is always f64.  G lanes per agent while the table fits
+// the group's candidates, else (or with SC_TRACK_LANE_PER_AGENT=1) one lane per agent with KMAX rows; an unlisted model id runs
+// as the DPCBF bicycle.
+template <bool AGENTS>
 static hipError_t launch_track(const TrackingArgs<AGENTS>& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                                int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                                void* tX, void* tU, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(TC);
-    auto kern = tracking_rollout_kernel<TIO, TC, KMAX, MODEL, AGENTS>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, (TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                       (TIO*)goal, (TIO*)table, (TIO*)u_last, ret, ret_step, (TIO*)tX, (TIO*)tU);
-    return hipGetLastError();
-}
-
-template <typename TIO, typename TC, int MODEL, bool AGENTS>
-static hipError_t launch_track_k(const TrackingArgs<AGENTS>& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                 int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
-                                 void* tX, void* tU, hipStream_t stream) {
     const char* env_lpa = std::getenv("SC_TRACK_LANE_PER_AGENT");        // read per call: the tests flip it
     const bool lane_per_agent = env_lpa && env_lpa[0] == '1';
-    if (!lane_per_agent) {
-        if (p.num_constraints <= 8 && M <= 32)
-            return launch_track_coop<TIO, TC, 8, MODEL, AGENTS>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
-        if (M <= 64)
-            return launch_track_coop<TIO, TC, 16, MODEL, AGENTS>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
-    }
-    if (p.num_constraints <= 8)
-        return launch_track<TIO, TC, 8, MODEL, AGENTS>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
-    return launch_track<TIO, TC, 16, MODEL, AGENTS>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream);
+    const bool f32 = p.qp.io_dtype == SC_DTYPE_F32;
+    hipError_t e = dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        using TIO = tag_t<decltype(tio)>;
+        using TC = double;
+        return dispatch_int_last<SC_MODEL_DYNAMIC_UNICYCLE2D, SC_MODEL_KINEMATIC_BICYCLE2D, SC_MODEL_UNICYCLE2D,
+                                 SC_MODEL_KINEMATIC_BICYCLE2D_C3BF, SC_MODEL_SINGLE_INTEGRATOR2D, SC_MODEL_DOUBLE_INTEGRATOR2D,
+                                 SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF>(p.qp.model_id, [&](auto model) {
+            constexpr int MODEL = decltype(model)::value;
+            auto coop = [&](auto g) {
+                constexpr int G = decltype(g)::value, APW = 64 / G;
+                const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(TC) + 64 * sizeof(int);
+                return launch<false>(tracking_coop_kernel<TIO, TC, G, MODEL, AGENTS>, (unsigned)((B + APW - 1) / APW), 64, lds, stream, p, B, M,
+                                     X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU);
+            };
+            auto lane = [&](auto kmax) {
+                const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(TC);
+                return launch(tracking_rollout_kernel<TIO, TC, decltype(kmax)::value, MODEL, AGENTS>, (unsigned)((B + 63) / 64), 64, lds, stream,
+                              p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU);
+            };
+            if (!lane_per_agent) {
+                if (p.num_constraints <= 8 && M <= 32) return coop(int_tag<8>{});
+                if (M <= 64) return coop(int_tag<16>{});
+            }
+            if (p.num_constraints <= 8) return lane(int_tag<8>{});
+            return lane(int_tag<16>{});
+        });
+    });
+    if (e != hipSuccess || !p.dyn_obs || M == 0) return e;
+    return advance_obstacle_table_launch(f32, table, M, p.n_steps, p.qp.dt, stream);
 }
-
-template <typename TIO, typename TC, bool AGENTS = false>
-static hipError_t launch_track_m(const TrackingArgs<AGENTS>& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                 int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
-                                 void* tX, void* tU, hipStream_t stream) {
-#define SC_TRACK_MODEL(ID) \
-    return launch_track_k<TIO, TC, ID, AGENTS>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, stream)
-    switch (p.qp.model_id) {
-        case SC_MODEL_DYNAMIC_UNICYCLE2D: SC_TRACK_MODEL(SC_MODEL_DYNAMIC_UNICYCLE2D);
-        case SC_MODEL_KINEMATIC_BICYCLE2D: SC_TRACK_MODEL(SC_MODEL_KINEMATIC_BICYCLE2D);
-        case SC_MODEL_UNICYCLE2D: SC_TRACK_MODEL(SC_MODEL_UNICYCLE2D);
-        case SC_MODEL_KINEMATIC_BICYCLE2D_C3BF: SC_TRACK_MODEL(SC_MODEL_KINEMATIC_BICYCLE2D_C3BF);
-        case SC_MODEL_SINGLE_INTEGRATOR2D: SC_TRACK_MODEL(SC_MODEL_SINGLE_INTEGRATOR2D);
-        case SC_MODEL_DOUBLE_INTEGRATOR2D: SC_TRACK_MODEL(SC_MODEL_DOUBLE_INTEGRATOR2D);
-        default: SC_TRACK_MODEL(SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF);
-    }
-#undef SC_TRACK_MODEL
-}
-
-// stream-ordered follow-up of a rollout over a moving table (tracking.hip)
-hipError_t advance_obstacle_table_launch(bool f32, void* table, int M, int n_steps, double dt, hipStream_t stream);
 
 }  // namespace sc

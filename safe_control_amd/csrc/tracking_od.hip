@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "od_qp.hpp"
+#include "sc_dispatch.hpp"
 #include "tracking_common.hpp"
 
 namespace sc {
@@ -189,47 +190,22 @@ __global__ __launch_bounds__(64) void tracking_od_rollout_kernel(
     }
 }
 
-template <typename TIO, int MODEL>
-static hipError_t launch_track_od(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                  int* wp_index, int* sm, void* goal, const void* table, void* u_last, int* ret, int* ret_step,
-                                  void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    auto kern = tracking_od_rollout_kernel<TIO, double, MODEL>;          // closed loops amplify rounding: arithmetic is always f64
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, (TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                       (TIO*)goal, (const TIO*)table, (TIO*)u_last, ret, ret_step, (TIO*)tX, (TIO*)tU, (TIO*)omega, (TIO*)min_h,
-                       (TIO*)tW);
-    return hipGetLastError();
-}
-
-template <typename TIO>
-static hipError_t launch_track_od_m(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                    int* wp_index, int* sm, void* goal, const void* table, void* u_last, int* ret, int* ret_step,
-                                    void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-#define SC_TOD(MODEL_) \
-    return launch_track_od<TIO, MODEL_>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream)
-    switch (p.track.qp.model_id) {
-        case SC_MODEL_DYNAMIC_UNICYCLE2D: SC_TOD(SC_MODEL_DYNAMIC_UNICYCLE2D);
-        case SC_MODEL_KINEMATIC_BICYCLE2D: SC_TOD(SC_MODEL_KINEMATIC_BICYCLE2D);
-        case SC_MODEL_KINEMATIC_BICYCLE2D_C3BF: SC_TOD(SC_MODEL_KINEMATIC_BICYCLE2D_C3BF);
-        default: SC_TOD(SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF);
-    }
-#undef SC_TOD
-}
-
 hipError_t tracking_od_launch(const sc_tracking_od_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                               int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                               void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-    const bool f32 = p.track.qp.io_dtype == SC_DTYPE_F32;
-    hipError_t e = f32 ? launch_track_od_m<float>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream)
-                       : launch_track_od_m<double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream);
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
+    hipError_t e = dispatch_io(p.track.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_DYNAMIC_UNICYCLE2D, SC_MODEL_KINEMATIC_BICYCLE2D, SC_MODEL_KINEMATIC_BICYCLE2D_C3BF,
+                                 SC_MODEL_KINEMATIC_BICYCLE2D_DPCBF>(p.track.qp.model_id, [&](auto model) {
+            // closed loops amplify rounding: arithmetic is always f64
+            return launch(tracking_od_rollout_kernel<tag_t<decltype(tio)>, double, decltype(model)::value>, blocks, 64, lds, stream, p, B, M, X,
+                          wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW);
+        });
+    });
     if (e != hipSuccess || !p.track.dyn_obs || M == 0) return e;
     // every block advanced its own LDS copy: the stream-ordered follow-up writes the table where n_steps put it
-    return advance_obstacle_table_launch(f32, table, M, p.track.n_steps, p.track.qp.dt, stream);
+    return advance_obstacle_table_launch(p.track.qp.io_dtype == SC_DTYPE_F32, table, M, p.track.n_steps, p.track.qp.dt, stream);
 }
 
 }  // namespace sc

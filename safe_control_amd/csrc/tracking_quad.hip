@@ -9,6 +9,7 @@
 // Arithmetic is f64; the caller's arrays are f32 or f64 (run-time switch: a handful of loads / stores per agent).
 #include <hip/hip_runtime.h>
 
+#include "sc_dispatch.hpp"
 #include "sc_math.hpp"
 #include "../../include/safe_control_amd.h"
 #include "mpc_vtol_solver.hpp"
@@ -297,22 +298,18 @@ hipError_t quadtrack_select_launch(const sc_quadtrack_params& p, long long B, in
                                    void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
     const unsigned blocks = (unsigned)((B + 63) / 64);
     const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    if (p.num_constraints <= 8)
-        hipLaunchKernelGGL(quadtrack_select_kernel<8>, dim3(blocks), dim3(64), lds, stream, p, B, M, X, wps, n_wp, wp_index, sm, goal, obs_table,
-                           ret, obs_out, goal_out, u_ref_out, track_out);
-    else
-        hipLaunchKernelGGL(quadtrack_select_kernel<16>, dim3(blocks), dim3(64), lds, stream, p, B, M, X, wps, n_wp, wp_index, sm, goal, obs_table,
-                           ret, obs_out, goal_out, u_ref_out, track_out);
-    return hipGetLastError();
+    auto go = [&](auto kern) {                                           // api.hip refuses a table above 64 KiB of LDS
+        return launch<false>(kern, blocks, 64, lds, stream, p, B, M, X, wps, n_wp, wp_index, sm, goal, obs_table, ret, obs_out, goal_out,
+                             u_ref_out, track_out);
+    };
+    return p.num_constraints <= 8 ? go(quadtrack_select_kernel<8>) : go(quadtrack_select_kernel<16>);
 }
 
 hipError_t quadtrack_apply_launch(const sc_quadtrack_params& p, long long B, int M, int step_index, void* X, const int* sm, const void* goal,
                                   const void* obs_table, const void* u, void* u_last, int* ret, int* ret_step, hipStream_t stream) {
     const unsigned blocks = (unsigned)((B + 63) / 64);
     const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    hipLaunchKernelGGL(quadtrack_apply_kernel, dim3(blocks), dim3(64), lds, stream, p, B, M, step_index, X, sm, goal, obs_table, u, u_last,
-                       ret, ret_step);
-    return hipGetLastError();
+    return launch<false>(quadtrack_apply_kernel, blocks, 64, lds, stream, p, B, M, step_index, X, sm, goal, obs_table, u, u_last, ret, ret_step);
 }
 
 }  // namespace sc

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "od_qp.hpp"
+#include "sc_dispatch.hpp"
 #include "sc_qp2.hpp"
 #include "tracking_common.hpp"
 
@@ -260,45 +261,24 @@ __global__ __launch_bounds__(64) void tracking_quad2d_rollout_kernel(
     }
 }
 
-template <typename TIO, int CTRL, int KMAX>
-static hipError_t launch_quad2d(const sc_tracking_quad2d_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                int* wp_index, int* sm, void* goal, const void* table, void* u_last, int* ret, int* ret_step,
-                                void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
-    auto kern = tracking_quad2d_rollout_kernel<TIO, double, CTRL, KMAX>;    // closed loops amplify rounding: arithmetic is always f64
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, B, M, (TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                       (TIO*)goal, (const TIO*)table, (TIO*)u_last, ret, ret_step, (TIO*)tX, (TIO*)tU, (TIO*)omega, (TIO*)min_h,
-                       (TIO*)tW);
-    return hipGetLastError();
-}
-
-template <typename TIO>
-static hipError_t launch_quad2d_c(const sc_tracking_quad2d_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
-                                  int* wp_index, int* sm, void* goal, const void* table, void* u_last, int* ret, int* ret_step,
-                                  void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-#define SC_TQ2(CTRL_, KMAX_) \
-    return launch_quad2d<TIO, CTRL_, KMAX_>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream)
-    if (p.controller == SC_QUAD2D_CTRL_OD_CBF_QP) SC_TQ2(SC_QUAD2D_CTRL_OD_CBF_QP, 1);
-    if (p.od.track.num_constraints <= 4) SC_TQ2(SC_QUAD2D_CTRL_CBF_QP, 4);
-    if (p.od.track.num_constraints <= 8) SC_TQ2(SC_QUAD2D_CTRL_CBF_QP, 8);
-    SC_TQ2(SC_QUAD2D_CTRL_CBF_QP, 16);
-#undef SC_TQ2
-}
-
 hipError_t tracking_quad2d_launch(const sc_tracking_quad2d_params& p, long long B, int M, void* X, const void* wps, const int* n_wp,
                                   int* wp_index, int* sm, void* goal, void* table, void* u_last, int* ret, int* ret_step,
                                   void* tX, void* tU, void* omega, void* min_h, void* tW, hipStream_t stream) {
-    const bool f32 = p.od.track.qp.io_dtype == SC_DTYPE_F32;
-    hipError_t e = f32 ? launch_quad2d_c<float>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream)
-                       : launch_quad2d_c<double>(p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW, stream);
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    const size_t lds = (size_t)(M > 0 ? M : 1) * 7 * sizeof(double);
+    hipError_t e = dispatch_io(p.od.track.qp.io_dtype, [&](auto tio) {
+        auto go = [&](auto ctrl, auto kmax) {                            // closed loops amplify rounding: arithmetic is always f64
+            return launch(tracking_quad2d_rollout_kernel<tag_t<decltype(tio)>, double, decltype(ctrl)::value, decltype(kmax)::value>, blocks, 64,
+                          lds, stream, p, B, M, X, wps, n_wp, wp_index, sm, goal, table, u_last, ret, ret_step, tX, tU, omega, min_h, tW);
+        };
+        if (p.controller == SC_QUAD2D_CTRL_OD_CBF_QP) return go(int_tag<SC_QUAD2D_CTRL_OD_CBF_QP>{}, int_tag<1>{});
+        if (p.od.track.num_constraints <= 4) return go(int_tag<SC_QUAD2D_CTRL_CBF_QP>{}, int_tag<4>{});
+        if (p.od.track.num_constraints <= 8) return go(int_tag<SC_QUAD2D_CTRL_CBF_QP>{}, int_tag<8>{});
+        return go(int_tag<SC_QUAD2D_CTRL_CBF_QP>{}, int_tag<16>{});
+    });
     if (e != hipSuccess || !p.od.track.dyn_obs || M == 0) return e;
     // every block advanced its own LDS copy: the stream-ordered follow-up writes the table where n_steps put it
-    return advance_obstacle_table_launch(f32, table, M, p.od.track.n_steps, p.od.track.qp.dt, stream);
+    return advance_obstacle_table_launch(p.od.track.qp.io_dtype == SC_DTYPE_F32, table, M, p.od.track.n_steps, p.od.track.qp.dt, stream);
 }
 
 }  // namespace sc

@@ -13,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sc_qp2.hpp"
+#include "sc_dispatch.hpp"
 #include "tracking_common.hpp"
 #include "tracking_sense_common.hpp"
 
@@ -272,64 +273,24 @@ __global__ __launch_bounds__(64) void tracking_sense_kernel(
     }
 }
 
-template <typename TIO, int KMAX, int MODEL>
-static hipError_t launch_sense(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, void* X, const void* wps,
-                               const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const void* utable,
-                               long long* seen, void* yaw, void* u_att, void* u_last, int* ret, int* ret_step, void* tX, void* tU,
-                               void* tYaw, long long* tSeen, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = ((size_t)M * 7 + (size_t)sp.n_unknown * 8 + 1) * sizeof(double);
-    auto kern = tracking_sense_kernel<TIO, double, KMAX, MODEL>;
-    if (lds > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, sp, B, M, (TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                       (TIO*)goal, (const TIO*)table, (const TIO*)utable, seen, (TIO*)yaw, (TIO*)u_att, (TIO*)u_last, ret, ret_step,
-                       (TIO*)tX, (TIO*)tU, (TIO*)tYaw, tSeen);
-    return hipGetLastError();
-}
-
-template <typename TIO, int MODEL>
-static hipError_t launch_sense_k(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, void* X, const void* wps,
-                                 const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const void* utable,
-                                 long long* seen, void* yaw, void* u_att, void* u_last, int* ret, int* ret_step, void* tX, void* tU,
-                                 void* tYaw, long long* tSeen, hipStream_t stream) {
-    if (p.num_constraints <= 8)
-        return launch_sense<TIO, 8, MODEL>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, u_last, ret,
-                                           ret_step, tX, tU, tYaw, tSeen, stream);
-    return launch_sense<TIO, 16, MODEL>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, u_last, ret,
-                                        ret_step, tX, tU, tYaw, tSeen, stream);
-}
-
-template <typename TIO>
-static hipError_t launch_sense_m(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, void* X, const void* wps,
-                                 const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const void* utable,
-                                 long long* seen, void* yaw, void* u_att, void* u_last, int* ret, int* ret_step, void* tX, void* tU,
-                                 void* tYaw, long long* tSeen, hipStream_t stream) {
-    switch (p.qp.model_id) {
-        case SC_MODEL_SINGLE_INTEGRATOR2D:
-            return launch_sense_k<TIO, SC_MODEL_SINGLE_INTEGRATOR2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw,
-                                                                     u_att, u_last, ret, ret_step, tX, tU, tYaw, tSeen, stream);
-        case SC_MODEL_DOUBLE_INTEGRATOR2D:
-            return launch_sense_k<TIO, SC_MODEL_DOUBLE_INTEGRATOR2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw,
-                                                                     u_att, u_last, ret, ret_step, tX, tU, tYaw, tSeen, stream);
-        default:
-            return launch_sense_k<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw,
-                                                                    u_att, u_last, ret, ret_step, tX, tU, tYaw, tSeen, stream);
-    }
-}
-
 hipError_t tracking_sense_launch(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, void* X, const void* wps,
                                  const int* n_wp, int* wp_index, int* sm, void* goal, const void* table, const void* utable,
                                  long long* seen, void* yaw, void* u_att, void* u_last, int* ret, int* ret_step, void* tX, void* tU,
                                  void* tYaw, long long* tSeen, hipStream_t stream) {
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    const size_t lds = ((size_t)M * 7 + (size_t)sp.n_unknown * 8 + 1) * sizeof(double);
     // arithmetic in f64 (closed loops amplify rounding), storage follows io_dtype -- as tracking_launch
-    if (p.qp.io_dtype == SC_DTYPE_F32)
-        return launch_sense_m<float>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, u_last, ret, ret_step,
-                                     tX, tU, tYaw, tSeen, stream);
-    return launch_sense_m<double>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, u_last, ret, ret_step,
-                                  tX, tU, tYaw, tSeen, stream);
+    return dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_SINGLE_INTEGRATOR2D, SC_MODEL_DOUBLE_INTEGRATOR2D, SC_MODEL_DYNAMIC_UNICYCLE2D>(p.qp.model_id, [&](auto model) {
+            auto go = [&](auto kmax) {
+                return launch(tracking_sense_kernel<tag_t<decltype(tio)>, double, decltype(kmax)::value, decltype(model)::value>, blocks, 64, lds,
+                              stream, p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, u_last, ret, ret_step,
+                              tX, tU, tYaw, tSeen);
+            };
+            if (p.num_constraints <= 8) return go(int_tag<8>{});
+            return go(int_tag<16>{});
+        });
+    });
 }
 
 }  // namespace sc

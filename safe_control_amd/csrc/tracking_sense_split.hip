@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sc_qp2.hpp"
+#include "sc_dispatch.hpp"
 #include "tracking_common.hpp"
 #include "tracking_sense_common.hpp"
 
@@ -268,90 +269,38 @@ static size_t sense_lds_bytes(int M, int Mu) {
     return ((rows > 7 ? rows : 7) + 1) * sizeof(double);
 }
 
-template <typename KERN>
-static hipError_t raise_lds_limit(KERN kern, size_t lds) {
-    if (lds <= 64 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-}
-
-template <typename TIO, int MODEL>
-static hipError_t launch_sense_select_m(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, const void* X,
-                                        const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
-                                        const void* utable, long long* seen, const void* yaw, void* u_att, const int* ret,
-                                        void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    const unsigned blocks = (unsigned)((B + 63) / 64);
-    const size_t lds = sense_lds_bytes(M, sp.n_unknown);
-    auto go = [&](auto kern) {
-        hipError_t e = raise_lds_limit(kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, sp, B, M, (const TIO*)X, (const TIO*)wps, n_wp, wp_index, sm,
-                           (TIO*)goal, (const TIO*)table, (const TIO*)utable, seen, (const TIO*)yaw, (TIO*)u_att, ret, (TIO*)obs_out,
-                           (TIO*)goal_out, (TIO*)u_ref_out, track_out);
-        return hipGetLastError();
-    };
-    if (p.num_constraints <= 8) return go(tracking_sense_select_kernel<TIO, double, 8, MODEL>);
-    return go(tracking_sense_select_kernel<TIO, double, 16, MODEL>);
-}
-
-template <typename TIO>
-static hipError_t launch_sense_select_t(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, const void* X,
-                                        const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
-                                        const void* utable, long long* seen, const void* yaw, void* u_att, const int* ret,
-                                        void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    switch (p.qp.model_id) {
-        case SC_MODEL_SINGLE_INTEGRATOR2D:
-            return launch_sense_select_m<TIO, SC_MODEL_SINGLE_INTEGRATOR2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen,
-                                                                            yaw, u_att, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-        case SC_MODEL_DOUBLE_INTEGRATOR2D:
-            return launch_sense_select_m<TIO, SC_MODEL_DOUBLE_INTEGRATOR2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen,
-                                                                            yaw, u_att, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-        default:
-            return launch_sense_select_m<TIO, SC_MODEL_DYNAMIC_UNICYCLE2D>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen,
-                                                                           yaw, u_att, ret, obs_out, goal_out, u_ref_out, track_out, stream);
-    }
-}
-
 hipError_t tracking_sense_select_launch(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, const void* X,
                                         const void* wps, const int* n_wp, int* wp_index, int* sm, void* goal, const void* table,
                                         const void* utable, long long* seen, const void* yaw, void* u_att, const int* ret,
                                         void* obs_out, void* goal_out, void* u_ref_out, int* track_out, hipStream_t stream) {
-    // arithmetic in f64 (closed loops amplify rounding), storage follows io_dtype -- as tracking_select_launch
-    if (p.qp.io_dtype == SC_DTYPE_F32)
-        return launch_sense_select_t<float>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, ret, obs_out,
-                                            goal_out, u_ref_out, track_out, stream);
-    return launch_sense_select_t<double>(p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, ret, obs_out,
-                                         goal_out, u_ref_out, track_out, stream);
-}
-
-template <typename TIO>
-static hipError_t launch_sense_apply_t(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, int step_index,
-                                       void* X, const int* sm, const void* goal, const void* table, const void* utable, void* yaw,
-                                       void* u_att, const void* u, const int* u_status, void* u_last, int* ret, int* ret_step,
-                                       hipStream_t stream) {
     const unsigned blocks = (unsigned)((B + 63) / 64);
     const size_t lds = sense_lds_bytes(M, sp.n_unknown);
-    auto go = [&](auto kern) {
-        hipError_t e = raise_lds_limit(kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, stream, p, sp, B, M, step_index, (TIO*)X, sm, (const TIO*)goal,
-                           (const TIO*)table, (const TIO*)utable, (TIO*)yaw, (TIO*)u_att, (const TIO*)u, u_status, (TIO*)u_last, ret,
-                           ret_step);
-        return hipGetLastError();
-    };
-    if (p.qp.model_id == SC_MODEL_SINGLE_INTEGRATOR2D) return go(tracking_sense_apply_kernel<TIO, double, SC_MODEL_SINGLE_INTEGRATOR2D>);
-    if (p.qp.model_id == SC_MODEL_DOUBLE_INTEGRATOR2D) return go(tracking_sense_apply_kernel<TIO, double, SC_MODEL_DOUBLE_INTEGRATOR2D>);
-    return go(tracking_sense_apply_kernel<TIO, double, SC_MODEL_DYNAMIC_UNICYCLE2D>);
+    // arithmetic in f64 (closed loops amplify rounding), storage follows io_dtype -- as tracking_select_launch
+    return dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_SINGLE_INTEGRATOR2D, SC_MODEL_DOUBLE_INTEGRATOR2D, SC_MODEL_DYNAMIC_UNICYCLE2D>(p.qp.model_id, [&](auto model) {
+            auto go = [&](auto kmax) {
+                return launch(tracking_sense_select_kernel<tag_t<decltype(tio)>, double, decltype(kmax)::value, decltype(model)::value>, blocks,
+                              64, lds, stream, p, sp, B, M, X, wps, n_wp, wp_index, sm, goal, table, utable, seen, yaw, u_att, ret, obs_out,
+                              goal_out, u_ref_out, track_out);
+            };
+            if (p.num_constraints <= 8) return go(int_tag<8>{});
+            return go(int_tag<16>{});
+        });
+    });
 }
 
 hipError_t tracking_sense_apply_launch(const sc_tracking_params& p, const sc_sense_params& sp, long long B, int M, int step_index,
                                        void* X, const int* sm, const void* goal, const void* table, const void* utable, void* yaw,
                                        void* u_att, const void* u, const int* u_status, void* u_last, int* ret, int* ret_step,
                                        hipStream_t stream) {
-    if (p.qp.io_dtype == SC_DTYPE_F32)
-        return launch_sense_apply_t<float>(p, sp, B, M, step_index, X, sm, goal, table, utable, yaw, u_att, u, u_status, u_last, ret,
-                                           ret_step, stream);
-    return launch_sense_apply_t<double>(p, sp, B, M, step_index, X, sm, goal, table, utable, yaw, u_att, u, u_status, u_last, ret,
-                                        ret_step, stream);
+    const unsigned blocks = (unsigned)((B + 63) / 64);
+    const size_t lds = sense_lds_bytes(M, sp.n_unknown);
+    return dispatch_io(p.qp.io_dtype, [&](auto tio) {
+        return dispatch_int_last<SC_MODEL_SINGLE_INTEGRATOR2D, SC_MODEL_DOUBLE_INTEGRATOR2D, SC_MODEL_DYNAMIC_UNICYCLE2D>(p.qp.model_id, [&](auto model) {
+            return launch(tracking_sense_apply_kernel<tag_t<decltype(tio)>, double, decltype(model)::value>, blocks, 64, lds, stream, p, sp, B, M,
+                          step_index, X, sm, goal, table, utable, yaw, u_att, u, u_status, u_last, ret, ret_step);
+        });
+    });
 }
 
 }  // namespace sc

@@ -182,6 +182,20 @@ SOLVE_SEEDS = {
     ('DoubleIntegrator2D', 5, True): 1000,   # 2 infeasible
     ('DoubleIntegrator2D', 16, False): 1000,   # 11 infeasible
     ('DoubleIntegrator2D', 16, True): 1000,   # 2 infeasible
+    # K = 4 (the KMAX = 4 kernel) and K = 20 (f32 rows per agent: 66 560 B of LDS, above the 64 KiB a kernel gets unasked)
+    ('DynamicUnicycle2D', 4, False): 1000, ('DynamicUnicycle2D', 4, True): 1000,
+    ('DynamicUnicycle2D', 20, False): 1000, ('DynamicUnicycle2D', 20, True): 1000,
+    ('KinematicBicycle2D', 4, False): 1000, ('KinematicBicycle2D', 4, True): 1003,
+    ('KinematicBicycle2D', 20, False): 1000, ('KinematicBicycle2D', 20, True): 1000,
+    ('KinematicBicycle2D_C3BF', 4, False): 1000, ('KinematicBicycle2D_C3BF', 4, True): 1000,
+    ('KinematicBicycle2D_C3BF', 20, False): 1000, ('KinematicBicycle2D_C3BF', 20, True): 1000,
+    ('KinematicBicycle2D_DPCBF', 4, False): 1000, ('KinematicBicycle2D_DPCBF', 4, True): 1000,
+    ('KinematicBicycle2D_DPCBF', 20, False): 1000, ('KinematicBicycle2D_DPCBF', 20, True): 1000,
+    ('Unicycle2D', 4, False): 1000, ('Unicycle2D', 4, True): 1000, ('Unicycle2D', 20, False): 1000, ('Unicycle2D', 20, True): 1000,
+    ('SingleIntegrator2D', 4, False): 1000, ('SingleIntegrator2D', 4, True): 1000,
+    ('SingleIntegrator2D', 20, False): 1000, ('SingleIntegrator2D', 20, True): 1000,
+    ('DoubleIntegrator2D', 4, False): 1000, ('DoubleIntegrator2D', 4, True): 1000,
+    ('DoubleIntegrator2D', 20, False): 1000, ('DoubleIntegrator2D', 20, True): 1000,
 }
 
 
@@ -222,9 +236,10 @@ def loop_case(name, obs, B, seed, moving=False):
     return dict(name=name, specs=specs, X0=np.array(X0), wl=wl, obs=obs, moving=moving)
 
 
-def oracle_loop(case, T, num_constraints=10, shift=0.0):
+def oracle_loop(case, T, num_constraints=10, shift=0.0, solve_fn=None):
     """One TrackingOracle per agent.  Returns per agent ``(X [n,4] after each of its n steps, last return code, n, final state
-    machine name, final goal index)``; ``shift`` moves every start state (the tie check of the module docstring)."""
+    machine name, final goal index)``; ``shift`` moves every start state (the tie check of the module docstring); ``solve_fn``
+    stands in for the CBF-QP (TrackingOracle: the position controller of the select / solve / apply loop)."""
     out = []
     m = model_id(case["name"])
     integ = m in (R.MODEL_SI, R.MODEL_DI)
@@ -235,7 +250,7 @@ def oracle_loop(case, T, num_constraints=10, shift=0.0):
         yaw0 = x0[nst] if integ else None
         xs = np.concatenate([x0[:nst], np.zeros(4 - nst)]) if integ else x0
         t = tracking.TrackingOracle(m, xs, ospec, dt=DT, obs=case["obs"], num_constraints=num_constraints,
-                                    enable_rotation=not integ, dyn_obs=case["moving"], cbf_param=cp, yaw0=yaw0)
+                                    enable_rotation=not integ, dyn_obs=case["moving"], cbf_param=cp, yaw0=yaw0, solve_fn=solve_fn)
         t.set_waypoints(case["wl"][i])
         Xs, ret = [], 0
         for _ in range(T):
@@ -246,6 +261,34 @@ def oracle_loop(case, T, num_constraints=10, shift=0.0):
         out.append((np.array(Xs), ret, len(Xs), t.state_machine, t.current_goal_index))
     return out
 
+
+# ---- every kernel the rollout's dispatch can select (test_every_kernel_of_the_rollout_dispatch) -----------------------------
+RUNG_B, RUNG_T = 65, 10            # one full wave and one lane; a partial last block of the 8- and 16-lane cooperative kernels
+BIG_M, BIG_B, BIG_T = 1171, 3, 2   # 1171 rows x 56 B = 65 576 B of LDS: the first table above the 64 KiB a kernel gets unasked
+
+
+def rung_case(name, per_agent, big=False):
+    """``RUNG_B`` agents on the first three circles of the six-circle scene, or (``big``) ``BIG_B`` agents on that scene followed
+    by 1165 small circles 500 m away.  Start states, waypoints and table are rounded to f32, so both storage types see the same
+    numbers and share one oracle run.  Without ``per_agent`` every agent carries the first agent's spec (the scalar entry point)."""
+    if big:
+        obs = np.zeros((BIG_M, 7))
+        obs[:6] = six_circle_scene()
+        obs[6:, 0] = 500.0 + np.arange(BIG_M - 6)
+        obs[6:, 1] = 500.0
+        obs[6:, 2] = 0.25
+    else:
+        obs = six_circle_scene()[:3]
+    case = loop_case(name, obs, BIG_B if big else RUNG_B, RUNG_SEEDS[name])
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    case["X0"], case["wl"], case["obs"] = f32(case["X0"]), [f32(w) for w in case["wl"]], f32(case["obs"])
+    if not per_agent:
+        case["specs"] = [dict(case["specs"][0]) for _ in case["specs"]]
+    return case
+
+
+# name -> seed of rung_case, chosen like LOOP_SEEDS: no agent's return code or finishing step moves with the start states
+RUNG_SEEDS = {name: 4000 for name in SOLVE_MODELS}
 
 # name -> seed of its closed-loop case; see the module docstring
 LOOP_SEEDS = {name: 2000 for name in SOLVE_MODELS}     # the first candidate passed for every model
@@ -266,7 +309,7 @@ def loop_setup(name):
 
 def _choose_solve():
     for name in SOLVE_MODELS:
-        for K in (5, 16):
+        for K in (4, 5, 16, 20):
             for shared in (False, True):
                 for seed in range(1000, 1400):
                     c = solve_case(name, K, shared, seed)
@@ -294,6 +337,24 @@ def _choose_loop(names):
             print("no loop seed for", name)
 
 
+def _choose_rung(names):
+    for name in names:
+        for seed in range(4000, 4200):
+            RUNG_SEEDS[name] = seed
+            ok = True
+            for per_agent in (True, False):
+                for big, T, ncs in ((False, RUNG_T, (8,)), (True, BIG_T, (8, 9))):
+                    for nc in ncs:
+                        c = rung_case(name, per_agent, big)
+                        base = [(r[1], r[2]) for r in oracle_loop(c, T, nc)]
+                        ok = ok and all([(r[1], r[2]) for r in oracle_loop(c, T, nc, shift=s)] == base for s in (1e-12, -1e-12))
+            if ok:
+                print(f"    {name!r}: {seed},", flush=True)
+                break
+        else:
+            print("no rung seed for", name)
+
+
 def _choose_dyn():
     for seed in range(3000, 3200):
         c = loop_case("KinematicBicycle2D_C3BF", six_circle_scene(), 40, seed, moving=True)
@@ -310,3 +371,5 @@ if __name__ == "__main__":                       # python tests/_agent_params_ca
     if "dyn" in what:
         _choose_dyn()
     _choose_loop([w for w in what if w in SOLVE_MODELS])
+    if "rung" in what:
+        _choose_rung(SOLVE_MODELS)

@@ -289,6 +289,43 @@ def oracle_from_fixture(z, tag):
     return o
 
 
+# ---- every kernel the sensing launchers can pick (the fused loop and the select / apply pair) -------------------------------------
+RUNG_UNKNOWN = np.array([[5.0, 5.0, 0.3125, 0, 0, 0, 0], [8.0, 9.0, 0.25, 0, 0, 0, 0], [2.5, 7.5, 0.375, 0, 0, 0, 0],
+                         [10.5, 6.5, 0.3125, 0, 0, 0, 0], [6.5, 11.5, 0.25, 0, 0, 0, 0]])     # f32 numbers
+
+
+def rung_records(case, T, num_constraints, make=None):
+    """One oracle per agent of a tests/_agent_params_cases.py rung_case (every agent the first agent's spec) with RUNG_UNKNOWN as its
+    unknown rows: the run() record of each, with `min_margin`.  ``make(*args, **kwargs)`` builds the oracle (default: UnknownEnvOracle)."""
+    import _agent_params_cases as AC
+    m, ospec, cp = AC.oracle_args(case["specs"][0])
+    out = []
+    for x0 in case["X0"]:
+        integ = m in (R.MODEL_SI, R.MODEL_DI)
+        nst = 2 if m == R.MODEL_SI else 4
+        xs = np.concatenate([x0[:nst], np.zeros(4 - nst)]) if integ else x0
+        o = (make or UnknownEnvOracle)(m, xs, ospec, dt=AC.DT, obs=case["obs"], unknown_obs=RUNG_UNKNOWN, num_constraints=num_constraints,
+                                       yaw0=x0[nst] if integ else None, cbf_param=cp)
+        o.set_waypoints(case["wl"][len(out)])
+        r = run(o, T)
+        r["min_margin"] = np.array(o.min_margin)
+        out.append(r)
+    return out
+
+
+def assert_records(ref, tX, tU, tY, tS, ret, rstep, sm, tol):
+    """What test_batch_against_the_oracle asserts of every agent, at rtol = atol = tol; no agent's sighting may be decided by less."""
+    for i, r in enumerate(ref):
+        assert float(r["min_margin"]) >= tol, f"agent {i}: a sighting decided by less than the comparison's tolerance"
+        n = len(r["ret"])
+        np.testing.assert_allclose(tX[:n, i], r["X"], rtol=tol, atol=tol, err_msg=f"agent {i}")
+        np.testing.assert_allclose(tU[:n, i], r["U"], rtol=tol, atol=tol, err_msg=f"agent {i}")
+        np.testing.assert_allclose(tY[:n, i], r["yaw"], rtol=tol, atol=tol, err_msg=f"agent {i}")
+        assert np.array_equal(tS[:n, i], r["mask"]), f"agent {i}: sighted rows"
+        last = int(r["ret"][-1])
+        assert ret[i] == last and rstep[i] == (n - 1 if last != 0 else -1) and sm[i] == r["sm"][-1], f"agent {i}"
+
+
 FLEET_B, FLEET_STEPS, FLEET_MU, FLEET_M = 130, 300, 33, 12
 FLEET_SPEC = {"radius": 0.25, "v_max": 1.0, "a_max": 1.0}
 FLEET_WPS = np.array([[2.0, 2.0], [2.0, 12.0], [12.0, 12.0], [12.0, 2.0]])

@@ -73,10 +73,12 @@ def check_against_oracle(case, ug, sg, hg, uo, so, ho, io):
 
 @pytest.mark.parametrize("io", ["f64", "f32"])
 @pytest.mark.parametrize("shared", [False, True], ids=["obs_per_agent", "obs_shared"])
-@pytest.mark.parametrize("K", [5, 16])
+@pytest.mark.parametrize("K", [4, 5, 16, 20])
 @pytest.mark.parametrize("name", AC.SOLVE_MODELS)
 def test_solve_against_the_oracle_per_agent(name, K, shared, io):
-    """B = 67 (two workgroups of the 64-lane kernel, one partial), every varying key drawn per agent, n_obs in [0, K]."""
+    """B = 67 (two workgroups of the 64-lane kernel, one partial), every varying key drawn per agent, n_obs in [0, K].  K = 4, 5 and
+    16 run the kernels with 4, 8 and any number of rows; with rows per agent K = 16 (f64) and K = 20 (f32) need more than 64 KiB of
+    LDS."""
     case = AC.solve_case(name, K, shared, AC.SOLVE_SEEDS[(name, K, shared)])
     ug, sg, hg, (Xs, us, os_) = gpu_solve(case, io)
     uo, so, ho, _ = AC.oracle_solve(case, Xs, us, os_)
@@ -176,12 +178,12 @@ def loop_reference(name):
     return case, T, AC.oracle_loop(case, T)
 
 
-def check_loop_against_oracle(out, ref, T):
+def check_loop_against_oracle(out, ref, T, rtol=1e-6):
     """traj_X within rtol = atol = 1e-6 (the existing figure of tests/test_tracking_gpu.py) up to each agent's last oracle step; ret,
     ret_step, state machine and goal index equal; every agent is compared."""
     codes = []
     for i, (Xo, ret_o, n, sm_o, gi_o) in enumerate(ref):
-        np.testing.assert_allclose(out["traj_X"][:n, i], Xo, rtol=1e-6, atol=1e-6, err_msg=f"agent {i}")
+        np.testing.assert_allclose(out["traj_X"][:n, i], Xo, rtol=rtol, atol=1e-6, err_msg=f"agent {i}")
         if ret_o != 0:
             assert out["ret"][i] == ret_o and out["ret_step"][i] == n - 1, (i, out["ret"][i], ret_o, out["ret_step"][i], n)
         else:
@@ -272,3 +274,46 @@ def test_moving_table_against_the_oracle(dispatch):
     for _ in range(T):
         want[:, 0:2] += want[:, 3:5] * AC.DT
     np.testing.assert_allclose(out["obs"], want, rtol=0, atol=1e-12)
+
+
+# ---- 7. every kernel the rollout's dispatch can select, in both parameter forms -----------------------------------------------
+@functools.lru_cache(maxsize=None)
+def rung_reference(name, per_agent, big, num_constraints):
+    """The case and its oracle runs, computed once and shared by the storage types and (small table: three rows, all of them
+    selected whatever num_constraints is) by the four dispatches; read-only."""
+    case = AC.rung_case(name, per_agent, big)
+    return case, AC.oracle_loop(case, AC.BIG_T if big else AC.RUNG_T, num_constraints)
+
+
+def check_rung(name, per_agent, big, num_constraints, io):
+    """One launch against the oracle.  f64 storage: the figures of check_loop_against_oracle.  f32 storage: the inputs are f32
+    numbers already (AC.rung_case) and the state stays in f64 registers for the whole launch, so the one difference is the
+    rounding of the recorded state to f32, at most 2^-24 relative: rtol grows by exactly that.  On the small table all three rows
+    are selected whatever KMAX is, so these cases hold every kernel instance to the oracle but cannot tell KMAX 8 from 16; the 1171-row
+    cases, where the oracle keeps the num_constraints nearest rows, can."""
+    T = AC.BIG_T if big else AC.RUNG_T
+    case, ref = rung_reference(name, per_agent, big, 8 if not big else num_constraints)
+    out = rollout(case, (T,), io, num_constraints, agent=per_agent, spec=case["specs"][0])
+    check_loop_against_oracle(out, ref, T, rtol=1e-6 + (2.0 ** -24 if io == "f32" else 0.0))
+
+
+@pytest.mark.parametrize("io", ["f64", "f32"])
+@pytest.mark.parametrize("per_agent", [True, False], ids=["agents", "scalar"])
+@pytest.mark.parametrize("dispatch,num_constraints", [("default", 8), ("default", 9), ("lane_per_agent", 8), ("lane_per_agent", 9)],
+                         indirect=["dispatch"])
+@pytest.mark.parametrize("name", AC.SOLVE_MODELS)
+def test_every_kernel_of_the_rollout_dispatch(name, dispatch, num_constraints, per_agent, io):
+    """tracking_coop_kernel with 8 lanes per agent (num_constraints 8) and 16 (9), tracking_rollout_kernel with KMAX 8 and 16, for
+    every model, storage type and parameter source: 65 agents x 10 steps on three circles against TrackingOracle."""
+    check_rung(name, per_agent, False, num_constraints, io)
+
+
+@pytest.mark.parametrize("io", ["f64", "f32"])
+@pytest.mark.parametrize("per_agent", [True, False], ids=["agents", "scalar"])
+@pytest.mark.parametrize("num_constraints", [8, 9])
+@pytest.mark.parametrize("name", AC.SOLVE_MODELS)
+def test_rollout_over_a_table_above_64_kib_of_lds(name, num_constraints, per_agent, io, monkeypatch):
+    """1171 rows = 65 576 B: the lane-per-agent kernels (M > 64) with the raised dynamic-LDS limit, KMAX 8 and 16; 3 agents x 2
+    steps against TrackingOracle."""
+    monkeypatch.delenv("SC_TRACK_LANE_PER_AGENT", raising=False)
+    check_rung(name, per_agent, True, num_constraints, io)

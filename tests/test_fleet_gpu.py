@@ -144,6 +144,37 @@ def test_one_step_mixed_states_against_oracle(io, tol):
     assert np.all(pub[ret != 0, 3] == 0) and np.all(pub[ret == 0, 3] == _np(ctl.X)[ret == 0, 3])
 
 
+# ---- every kernel the fleet step's dispatch can select --------------------------------------------------------------------
+@pytest.mark.parametrize("io,tol", [("f64", 1e-9), ("f32", 1e-5)])           # the one-step figures of the test above
+@pytest.mark.parametrize("num_constraints", [8, 9], ids=["8_lanes_per_agent", "16_lanes_per_agent"])
+@pytest.mark.parametrize("model", sca.BatchedFleetTrackingController.MODELS)
+def test_every_kernel_of_the_fleet_dispatch(model, num_constraints, io, tol):
+    """tracking_fleet_kernel with 8 lanes per agent (num_constraints <= 8 and M + K_nb <= 32) and with 16, for every model and
+    storage type: 65 agents (a partial last block in both forms), a 3-row moving table, 8 neighbours, one step against the oracle."""
+    cfg = dict(model=model, n=65, m=3, seed=21, **({"goal_dist": (2.0, 6.0), "spacing": 2.0} if model == "DynamicUnicycle2D" else {}))
+    X0, wps, obs = _scene(cfg)
+    wps = list(wps)
+    if io == "f32":
+        X0, obs = X0.astype(np.float32).astype(np.float64), obs.astype(np.float32).astype(np.float64)
+        wps = [np.asarray(w).astype(np.float32).astype(np.float64) for w in wps]
+    spec = {"model": model}
+    ctl = sca.BatchedFleetTrackingController(X0, dict(spec), obs=obs, dyn_obs=True, neighbours=8, num_constraints=num_constraints,
+                                             io_dtype=io, device=DEV)
+    ctl.set_waypoints(wps)
+    orc = FO.FleetOracle(model, X0, dict(spec), wps, obs=obs, dyn_obs=True, K_nb=8, num_constraints=num_constraints,
+                         io=np.float32 if io == "f32" else np.float64)
+    ctl.control_step(1)
+    orc.step()
+    o = orc.state()
+    np.testing.assert_array_equal(_np(ctl.ret), o["ret"])
+    np.testing.assert_array_equal(_np(ctl.cause), o["cause"])
+    np.testing.assert_array_equal(_np(ctl.state_machine), o["sm"])
+    np.testing.assert_allclose(_np(ctl.X), o["X"], rtol=tol, atol=tol)
+    fin = np.isfinite(o["min_sep"])
+    np.testing.assert_array_equal(np.isinf(_np(ctl.min_sep)), ~fin)
+    np.testing.assert_allclose(_np(ctl.min_sep)[fin], o["min_sep"][fin], rtol=0, atol=tol)
+
+
 # ---- closed loops -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", list(_LOOPS))
 def test_closed_loop_against_oracle(key, loop_oracles):

@@ -588,3 +588,70 @@ def test_collision_cone_bicycles_closed_loop_with_mpc(model_name, model_id):
                 break
         n_track += state.get("n", 0)
     assert n_track >= T
+
+
+# ---- every kernel the select / apply launchers can pick, held to the oracle loop without an MPC in between ------------------------
+import _agent_params_cases as AC  # noqa: E402
+
+
+def stand_in_input(xy, goal, rows):
+    """A position controller that is a few additions (numpy here, torch below): towards the goal, shifted by two symmetric sums over
+    the selected obstacle rows (padding rows have radius 0 and drop out), so that a wrong row, goal or state shows in the next state."""
+    w = rows[..., 2].sum(-1)
+    wx = (rows[..., 0] * rows[..., 2]).sum(-1)
+    d = 0.3 * (goal - xy)
+    return d.clip(-0.5, 0.5) + 0.01 * (w[..., None] * np.array([1.0, -1.0]) + 0.1 * wx[..., None])
+
+
+class StandInSolver:
+    """What ``_control_step_split`` asks of an MPC object: solve(X, u_prev, goal, obs) -> (u, status, iterations)."""
+
+    def solve(self, X, u_prev, goal, obs):
+        xy, g, o = X[:, :2].double(), goal.double(), obs.double()
+        w = o[:, :, 2].sum(1)
+        wx = (o[:, :, 0] * o[:, :, 2]).sum(1)
+        u = (0.3 * (g - xy)).clamp(-0.5, 0.5) + 0.01 * (w[:, None] * torch.tensor([1.0, -1.0], dtype=torch.float64, device=X.device) + 0.1 * wx[:, None])
+        z = torch.zeros(len(X), dtype=torch.int32, device=X.device)
+        return u.to(X.dtype), z, z
+
+
+def oracle_stand_in(K):
+    from oracle import mpc_cbf as M
+
+    def solve_fn(X, cref, nobs):
+        if cref["state_machine"] != "track":
+            return np.asarray(cref["u_ref"], dtype=np.float64).reshape(-1), 0
+        rows = M.pad_obstacles(None if nobs is None else list(nobs), K)
+        return stand_in_input(np.asarray(X[:2], dtype=np.float64), np.asarray(cref["goal"][:2], dtype=np.float64), rows), 0
+    return solve_fn
+
+
+@pytest.mark.parametrize("io", ["f64", "f32"])
+@pytest.mark.parametrize("big", [False, True], ids=["m3", "m1171"])
+@pytest.mark.parametrize("num_constraints", [8, 9])
+@pytest.mark.parametrize("name", ["DynamicUnicycle2D", "Unicycle2D", "SingleIntegrator2D", "DoubleIntegrator2D", "KinematicBicycle2D"])
+def test_every_kernel_of_the_select_and_apply_launchers(name, num_constraints, big, io):
+    """tracking_select_kernel with KMAX 8 (num_constraints 8) and 16 (9) and tracking_apply_kernel, for the five models they are built
+    for and both storage types, in the loop they serve with StandInSolver as its position controller: 65 agents x 10 steps on three
+    circles, and 3 agents x 2 steps on 1171 rows (65 576 B of LDS: the raised dynamic-LDS limit), against TrackingOracle with the same
+    stand-in behind solve_fn.  f64: atol 5e-6, this file's figure for the select / solve / apply loop.  f32: the loop stores the state
+    as f32 after every step, at most 2^-24 * 16 = 9.5e-7 per step on coordinates below 16; over n <= 10 steps these add up and pass
+    through dynamics whose step Jacobian is 1 + O(dt), allowed for by a factor 2: atol = 5e-6 + 2 n 9.5e-7."""
+    T = AC.BIG_T if big else AC.RUNG_T
+    case = AC.rung_case(name, False, big)
+    spec = dict(case["specs"][0], num_constraints=num_constraints)
+    integ = name in ("SingleIntegrator2D", "DoubleIntegrator2D")
+    ctl = sca.BatchedTrackingController(case["X0"], spec, controller_type={"pos": "mpc_cbf"}, obs=case["obs"], io_dtype=io, enable_rotation=not integ)
+    ctl.mpc, ctl.mpc_ms = StandInSolver(), None
+    ctl.set_waypoints(case["wl"])
+    ret, tX, tU = ctl.control_step(T, record=True)
+    tX, ret, rstep = tX.double().cpu().numpy(), ret.cpu().numpy(), ctl.ret_step.cpu().numpy()
+    ref = AC.oracle_loop(case, T, num_constraints, solve_fn=oracle_stand_in(num_constraints))
+    atol = 5e-6 + (2 * T * 16 * 2.0 ** -24 if io == "f32" else 0.0)
+    n_track = 0
+    for i, (Xo, ret_o, n, sm_o, gi_o) in enumerate(ref):
+        np.testing.assert_allclose(tX[:n, i], Xo, rtol=0, atol=atol, err_msg=f"agent {i}")
+        assert ret[i] == ret_o and rstep[i] == (n - 1 if ret_o != 0 else -1), i
+        assert int(ctl.state_machine[i].item()) == SM[sm_o] and int(ctl.current_goal_index[i].item()) == gi_o, i
+        n_track += sm_o == "track"
+    assert n_track > 0 or big                                     # the stand-in really ran (three agents may all be turning or stopped)

@@ -129,6 +129,34 @@ def test_oracle_parity_f32_storage_first_launch(name):
     assert keep.sum() >= 0.98 * B and (r["n"] < LAUNCHES[0]).any()
 
 
+def big_table(obs):
+    """The scene's rows, then small circles 500 m away up to 1171 rows: 65 576 B of LDS, the first table above the 64 KiB a kernel
+    gets without the raised limit.  f32 numbers, so both storage types read the same table."""
+    far = np.zeros((1171 - len(obs), 7))
+    far[:, 0], far[:, 1], far[:, 2] = 500.0 + np.arange(len(far)), 500.0, 0.25
+    return np.vstack([obs, far]).astype(np.float32).astype(np.float64)
+
+
+@pytest.mark.parametrize("io,tol", [("f64", 1e-6), ("f32", 3e-6)])           # the figures of the two parity tests above
+@pytest.mark.parametrize("name", ["du", "kb", "c3bf_moving", "dpcbf_moving"])
+def test_table_above_64_kib_of_lds(name, io, tol):
+    """M = 1171 rows, 3 agents, 2 steps in one launch against the oracle: every model's kernel with the raised dynamic-LDS limit."""
+    model, extra, odp, rot, dyn, seed = RUNS[name]
+    X0, wps, obs = O.scene(model, B, seed, moving=dyn)
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    X0, wps, obs = f32(X0[:3]), f32(wps[:3]), big_table(obs)
+    base = dict(O.DU_SPEC if model == "DynamicUnicycle2D" else O.KB_SPEC, model=model, **extra)
+    cfg = dict(model=model, spec=base, od_param=odp, dt=0.05, dyn_obs=dyn, enable_rotation=rot)
+    ctl = sca.BatchedTrackingController(X0, dict(base, **{"cbf_" + k: v for k, v in odp.items()}), controller_type=OD, dt=0.05,
+                                        enable_rotation=rot, obs=obs, dyn_obs=dyn, io_dtype=io)
+    ctl.set_waypoints(list(wps))
+    assert ctl.obs.shape[0] * 56 > 64 * 1024
+    traj = rollout(ctl, (2,))
+    r = O._run_slice(cfg, X0, wps, obs, 2)
+    keep = compare(ctl, traj, r, tol, 2, full=(io == "f64"))
+    assert keep.all()
+
+
 def test_no_obstacles_still_clips_to_the_input_box():
     """obs None: the optimal-decay QP is solved with a zero row, so the applied turn rate is clipped to w_max, where the same scene
     under 'cbf_qp' passes u_ref through unclipped (csrc/tracking.hip, M == 0)."""

@@ -122,10 +122,10 @@ def test_oracle_parity_f64(name):
         assert np.array_equal(ctl.obs.cpu().numpy(), obs)
 
 
-@pytest.mark.parametrize("name", ["cbf_k3", "od_p1", "cbf_k3_moving", "od_p1_moving"])
+@pytest.mark.parametrize("name", ["cbf_k3", "cbf_k6", "cbf_k10", "od_p1", "cbf_k3_moving", "od_p1_moving"])
 def test_oracle_parity_f32_storage_first_launch(name):
     """f32 storage, f64 arithmetic: the first launch against the oracle run from the states, waypoints and table re-read from the
-    device, at 3e-6 as tests/test_tracking_od_gpu.py does."""
+    device, at 3e-6 as tests/test_tracking_od_gpu.py does.  K = 3, 6 and 10: the kernels built for up to 4, 8 and 16 rows."""
     ctl, cfg, _, _, _ = setup(name, io="f32")
     assert ctl.X.dtype == torch.float32 and ctl.obs.dtype == torch.float32
     X0 = ctl.X.double().cpu().numpy()
@@ -136,6 +136,34 @@ def test_oracle_parity_f32_storage_first_launch(name):
     r = Q.run_many(cfg, X0, wps, obs, LAUNCHES[0])
     keep = compare(ctl, traj, r, 3e-6, LAUNCHES[0], full=False)
     assert keep.sum() >= 0.98 * B and (r["n"] < LAUNCHES[0]).any()
+
+
+def big_table(obs):
+    """The scene's rows, then small circles 500 m away up to 1171 rows: 65 576 B of LDS, the first table above the 64 KiB a kernel
+    gets without the raised limit.  f32 numbers, so both storage types read the same table."""
+    far = np.zeros((1171 - len(obs), 7))
+    far[:, 0], far[:, 1], far[:, 2] = 500.0 + np.arange(len(far)), 500.0, 0.25
+    return np.vstack([obs, far]).astype(np.float32).astype(np.float64)
+
+
+@pytest.mark.parametrize("io,tol", [("f64", 1e-6), ("f32", 3e-6)])           # the figures of the two parity tests above
+@pytest.mark.parametrize("name", ["cbf_k3", "cbf_k6", "cbf_k10", "od_p1"])
+def test_table_above_64_kib_of_lds(name, io, tol):
+    """M = 1171 rows, 3 agents, 2 steps in one launch against the oracle: the optimal-decay kernel and the CBF-QP kernels for up to 4,
+    8 and 16 rows with the raised dynamic-LDS limit."""
+    ctrl, K, odp, dyn, seed = RUNS[name]
+    X0, wps, obs = Q.scene(B, seed, moving=dyn)
+    f32 = lambda a: np.asarray(a, dtype=np.float32).astype(np.float64)
+    X0, wps, obs = f32(X0[:3]), f32(wps[:3]), big_table(obs)
+    cfg = dict(controller=ctrl, spec=dict(Q.SPEC), param=odp, num_constraints=K, dt=0.05, dyn_obs=dyn)
+    spec = dict(Q.SPEC, num_constraints=K, **{"cbf_" + k: v for k, v in odp.items()})
+    ctl = sca.BatchedTrackingController(X0, spec, controller_type={"pos": ctrl}, dt=0.05, obs=obs, dyn_obs=dyn, io_dtype=io)
+    ctl.set_waypoints(list(wps))
+    assert ctl.obs.shape[0] * 56 > 64 * 1024
+    traj = rollout(ctl, (2,))
+    r = Q._run_slice(cfg, X0, wps, obs, 2)
+    keep = compare(ctl, traj, r, tol, 2, full=(io == "f64"))
+    assert keep.all()
 
 
 def quadtrack_select(ctl, K):

@@ -114,6 +114,29 @@ def test_batch_against_the_oracle(num_constraints):
     assert len(excluded) <= 2
 
 
+@pytest.mark.parametrize("io", ["f64", "f32"])
+@pytest.mark.parametrize("big", [False, True], ids=["m3", "m1171"])
+@pytest.mark.parametrize("num_constraints", [8, 9])                         # KMAX 8 and 16
+@pytest.mark.parametrize("name", sca.BatchedSensingTrackingController.MODELS)
+def test_every_kernel_of_the_sensing_launcher(name, num_constraints, big, io):
+    """tracking_sense_kernel for its three models, KMAX 8 and 16 and both storage types: 65 agents x 10 steps on three known and five
+    unknown circles, and 3 agents x 2 steps on a known table of 1171 rows (65 576 B of LDS: the raised dynamic-LDS limit), one launch
+    against the oracle.  f64: 1e-7, the figure of the test above.  f32: the inputs are f32 numbers and the state stays in f64
+    registers for the whole launch, so the records differ by their rounding to f32 alone, 2^-24 relative: 1e-7 + 2^-24."""
+    import _agent_params_cases as AC
+    T = AC.BIG_T if big else AC.RUNG_T
+    case = AC.rung_case(name, False, big)
+    ctl = sca.BatchedSensingTrackingController(case["X0"], dict(case["specs"][0], num_constraints=num_constraints), obs=case["obs"],
+                                               unknown_obs=O.RUNG_UNKNOWN, io_dtype=io)
+    ctl.set_waypoints(case["wl"])
+    ret, tX, tU, tY, tS = ctl.control_step(T, record=True)
+    ref = O.rung_records(case, T, num_constraints)
+    O.assert_records(ref, cpu(tX.double()), cpu(tU.double()), cpu(tY.double()), u64(tS), cpu(ret), cpu(ctl.ret_step), cpu(ctl.state_machine),
+                     1e-7 + (2.0 ** -24 if io == "f32" else 0.0))
+    if not big:
+        assert any(r["mask"].any() for r in ref)                             # some agent sighted an unknown row
+
+
 # ---- 3. the edges of Mu -----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model", ["DynamicUnicycle2D", "DoubleIntegrator2D"])
 def test_no_unknown_rows_is_the_plain_rollout_bit_for_bit(golden_dir, monkeypatch, model):

@@ -165,6 +165,44 @@ def test_sensing_against_the_split_oracle(monkeypatch, num_constraints):
     assert (last_mask >> np.uint64(32)).astype(bool).any() and (last_mask & np.uint64(0xFFFFFFFF)).astype(bool).any()
 
 
+@pytest.mark.parametrize("io", ["f64", "f32"])
+@pytest.mark.parametrize("big", [False, True], ids=["m3", "m1171"])
+@pytest.mark.parametrize("num_constraints", [8, 9])                         # KMAX 8 and 16
+@pytest.mark.parametrize("name", sca.BatchedSensingMPCTrackingController.MODELS)
+def test_every_kernel_of_the_sensing_select_and_apply_launchers(monkeypatch, name, num_constraints, big, io):
+    """tracking_sense_select_kernel (KMAX 8 and 16) and tracking_sense_apply_kernel for their three models and both storage types, in
+    the loop they serve with the batched CBF-QP standing in for the MPC (as above): 65 agents x 10 steps on three known and five
+    unknown circles, and 3 agents x 2 steps on a known table of 1171 rows (65 576 B of LDS: the raised dynamic-LDS limit), against
+    the split oracle.  f64: 1e-7, the figure of the test above.  f32: the loop stores state and heading as f32 after every step, at
+    most 2^-24 * 16 = 9.5e-7 per step on values below 16; over n <= 10 steps these add up and pass through dynamics whose step
+    Jacobian is 1 + O(dt), allowed for by a factor 2: 1e-7 + 2 n 9.5e-7."""
+    import _agent_params_cases as AC
+    T = AC.BIG_T if big else AC.RUNG_T
+    case = AC.rung_case(name, False, big)
+    spec = dict(case["specs"][0], num_constraints=num_constraints)
+    ctl = sca.BatchedSensingMPCTrackingController(case["X0"], dict(spec), controller_type={"pos": "mpc_cbf", "att": "velocity_tracking_yaw"},
+                                                  obs=case["obs"], unknown_obs=O.RUNG_UNKNOWN, io_dtype=io)
+    ctl.set_waypoints(case["wl"])
+    qp = sca.BatchedCBFQP(dict(spec), io_dtype=io, compute_dtype="f64")
+    zeros = torch.zeros(ctl.B, dtype=torch.int32, device=ctl.device)
+
+    class StandIn:
+        def solve(self, X_in, up_in, goal_in, obs_in):
+            u, st, _ = qp.solve(ctl.X, ctl.u_ref, ctl.obs_sel)
+            return torch.where((st == 0).unsqueeze(1), u, ctl.u_ref).contiguous(), zeros, zeros
+
+    monkeypatch.setattr(ctl, "_split_solver", lambda: StandIn())
+    ret, tX, tU, tY, tS = ctl.control_step(T, record=True)
+
+    def make(*a, **k):
+        o = S.UnknownEnvSplitOracle(*a, solve_fn=lambda *x: None, **k)
+        o.split_solve_fn = S.padded_cbf_qp_solve_fn(o)
+        return o
+    ref = O.rung_records(case, T, num_constraints, make)
+    O.assert_records(ref, cpu(tX.double()), cpu(tU.double()), cpu(tY.double()), u64(tS), cpu(ret), cpu(ctl.ret_step), cpu(ctl.state_machine),
+                     1e-7 + (2 * T * 16 * 2.0 ** -24 if io == "f32" else 0.0))
+
+
 # ---- 3. the feature: closed loops with the MPC kernels ----------------------------------------------------------------------------
 def feature_controller(sc, unknown=True, io_dtype="f64"):
     ctype = {"pos": "mpc_cbf"}
